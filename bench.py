@@ -7,7 +7,11 @@ KITTI-like data resident in HBM (BASELINE.json metric / configs[1]; SURVEY.md se
     python bench.py --gpus N ...          (no launcher: spawns the N ranks itself through torch.distributed.run on a free port)
 
 One rank per GPU (RCCL over xGMI); the only exchange is the bucketed gradient all-reduce overlapped with the encoder backward.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE short JSON line on stdout (the contract fields, config and scalar summaries: emit()) and the full line below, with
+its per-kernel tables and nested configs, as `[bench-detail] {...}` on stderr.
+
+  --dump-outputs DIR  after the timed steps: the last step's loss, a fixed sample of the parameters / gradients / Adam moments and the
+                    BatchNorm buffers as DIR/<name>.npy (dump_outputs), for comparing two builds run with the same arguments.
 
   --scaling strong  (default) the literal metric of BASELINE.json ("b32 @1/2/4/8 GPU"): --global-batch 32 split into 32/N images per
                     rank, total work fixed as N grows; `value` is that rate.  At N = 1 this IS b32 on one GPU.  With N > 1 the line also
@@ -420,6 +424,8 @@ def main():
                          "`other_configs` / `strong_1gpu` (auto: on for the plain `python bench.py [--gpus 1]` call)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only plumbing check of the N>1 path: build the net, the arena, the buckets, one fake all-reduce cycle, tear down")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     import torch.distributed as dist
@@ -573,6 +579,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, opt, state["nets"])
 
     # ---- secondary timing (not `value`): the same step with the fp32 matrix instruction in the Winograd kernels, so that the line
     #      carries both numbers from one run on one box
@@ -784,8 +792,7 @@ def main():
     except Exception:                                           # noqa: BLE001
         pass
     if rank == 0:
-        print(json.dumps(line))
-        sys.stdout.flush()
+        emit(line)
     if world > 1:
         dist.destroy_process_group()
 
@@ -896,8 +903,7 @@ def rccl_selfcheck(line, dev, rank, world, timeout_s=90.0):
     def bail():
         result["status"] = "timeout after %.0f s (own-RCCL path blocked); the line above it is unaffected" % timeout_s
         if rank == 0:
-            print(json.dumps(line))
-            sys.stdout.flush()
+            emit(line)
         os._exit(0)
 
     dog = threading.Timer(timeout_s, bail)
@@ -1017,6 +1023,73 @@ def pmc_traffic_source(kernel):
     if f is None or pmc_traffic(kernel) is None:
         return None
     return "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the build that was profiled, not measured in this run)" % os.path.basename(f)
+
+
+DUMP_SAMPLE = 1 << 21            # entries kept of each parameter-arena array (8 MB in fp32): four of them stay far below 64 MB
+
+
+def dump_outputs(out_dir, loss, opt, nets):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy, so that two builds run with the same arguments
+    (same seeded inputs and initial weights) can be compared output for output:
+      loss.npy          the step's loss (float64, shape ())
+      params.npy        the parameters after its Adam update
+      grads.npy         the gradients its backward pass wrote
+      exp_avg.npy       Adam's first moment after the update
+      exp_avg_sq.npy    Adam's second moment after the update
+      sample_index.npy  the positions of the flat parameter arena (every net of the config, in its fixed order) the four arrays above
+                        hold, as float64 (exact): every position, or above DUMP_SAMPLE entries the same fixed sample for all four
+                        (numpy default_rng(0), ascending); those four are float32
+      buffers.npy       the BatchNorm running statistics and batch counters of every net, in state_dict order (float64)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = opt.arena
+    if a.flat_p.is_cuda:
+        torch.cuda.synchronize()
+    n = a.flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(n)
+    tidx = torch.from_numpy(idx).to(a.flat_p.device)
+    arrays = {"loss": np.asarray(float(loss.detach().double().item()), dtype=np.float64),
+              "sample_index": idx.astype(np.float64)}
+    for name, t in (("params", a.flat_p), ("grads", a.flat_g), ("exp_avg", opt.exp_avg), ("exp_avg_sq", opt.exp_avg_sq)):
+        arrays[name] = t.detach().index_select(0, tidx).float().cpu().numpy()
+    bufs = [b.detach().reshape(-1).double().cpu() for net in nets for b in net.buffers()]
+    arrays["buffers"] = (torch.cat(bufs) if bufs else torch.zeros(0, dtype=torch.float64)).numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= 64 << 20, "dump of %d bytes exceeds 64 MB" % total
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+# what the printed line keeps of each nested block; everything else goes to the detail line on stderr
+HEADLINE_KEEP = {
+    "roofline": ("kernel", "achieved", "peak", "unit", "frac", "fp32_equivalent_achieved", "credited_achieved", "credited_frac"),
+    "roofline_hbm": ("kernel", "achieved", "peak", "unit", "frac", "frac_of_measured_peak"),
+    "cpu_baseline": ("value", "unit", "cores", "kind"),
+}
+HEADLINE_DROP = ("other_configs", "strong_1gpu")
+
+
+def emit(line):
+    """Print the result: the full line (per-kernel tables, the CPU sample, the nested configs) as `[bench-detail] {...}` on stderr,
+    then ONE short JSON line on stdout -- the contract fields, the run's configuration and the scalar summaries -- that a reader
+    keeping only the last few KB of stdout still parses."""
+    if line is None:
+        return
+    print("[bench-detail] " + json.dumps(line), file=sys.stderr)
+    sys.stderr.flush()
+    short = {}
+    for k, v in line.items():
+        if k in HEADLINE_DROP:
+            continue
+        if k in HEADLINE_KEEP and isinstance(v, dict):
+            v = {kk: v.get(kk) for kk in HEADLINE_KEEP[k]}
+        short[k] = v
+    short["detail"] = "stderr: [bench-detail]"
+    print(json.dumps(short))
+    sys.stdout.flush()
 
 
 def _quiet_init(net):
