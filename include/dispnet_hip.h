@@ -574,6 +574,24 @@ int dn_u8_normalize_flip(const uint8_t* src, const uint8_t* flip, int32_t B, int
 int dn_flip_w(const float* src, const uint8_t* flip, int32_t B, int32_t H, int32_t W, float* dst, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * NYU Depth v2 input chain (reference datasets/nyu_depth_v2.py:76-110).  Training: raw = the stored samples [B,5,H0,W0] fp32 (RGB 0..255,
+ * depth in metres, 0/1 mask); params = double[B][8] {flip, angle in degrees, crop row, crop column, zoom s >= 1, colour gain, 0, 0},
+ * drawn on the host.  dn_nyu_prefilter writes minmax = float[B][DN_NYU_MINMAX_CHUNKS][2] partial (min, max) over all five channels and
+ * coef = double[B][4][H0][W0], the cubic B-spline coefficients (mirror boundaries, fp64) of the flipped RGB + depth (W0 <= 1024).
+ * dn_nyu_train_resample then writes, per output pixel of the OH x OW crop: the rotated value (scipy.ndimage.rotate order 3, mode
+ * 'constant') rounded to fp32 and clipped to [min, max], zoomed bilinearly toward the top-left corner (skimage warp, fp64), depth / s,
+ * RGB * gain clipped to [0, 255], cast to fp32 and normalised: img[B,3,OH,OW] = (x - mean[c]) / std[c] (IEEE fp32), depth[B,OH,OW].
+ * Validation: dn_nyu_val_resize = scipy.ndimage.zoom(order=1) of src [B,3,IH,IW] fp32 to [B,3,OH,OW], rounded to fp32, then normalised.
+ * mean_host / std_host: 3 floats each on the host.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DN_NYU_MINMAX_CHUNKS 16
+int dn_nyu_prefilter(const float* raw, const double* params, int32_t B, int32_t H0, int32_t W0, double* coef, float* minmax, dn_stream_t stream);
+int dn_nyu_train_resample(const double* coef, const float* minmax, const double* params, int32_t B, int32_t H0, int32_t W0, int32_t OH,
+                          int32_t OW, const float* mean_host, const float* std_host, float* img, float* depth, dn_stream_t stream);
+int dn_nyu_val_resize(const float* src, int32_t B, int32_t IH, int32_t IW, int32_t OH, int32_t OW, const float* mean_host, const float* std_host,
+                      float* dst, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Attainable-peak probes (SURVEY.md section 8d "Peaks"; used by bench.py only): a float4 streaming copy of n floats
  * (n % 4 == 0, 16-byte aligned; moves 8*n bytes) and a register-resident v_mfma_f32_32x32x2_f32 loop
  * (out: blocks*256 floats; dn_ubench_mfma_f32_flops = the FLOPs one launch executes).

@@ -13,7 +13,7 @@ LIB_PATH = pathlib.Path(os.environ.get("DISPNET_HIP_LIB", _PKG / "libdispnet_hip
 # ABI version this binding was written against (include/dispnet_hip.h: dn_version(), bumped on any signature / struct change).
 # load() refuses a library that reports anything else: a stale .so (DISPNET_HIP_LIB, a build that did not re-run) would otherwise
 # read struct fields past the end of what this binding fills in and mis-marshal arguments -- silent memory corruption, not an error.
-EXPECTED_ABI = 17
+EXPECTED_ABI = 18
 
 DN_MAX_OPERANDS = 3
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_ELU, ACT_SIGMOID_AFFINE = 0, 1, 2, 3, 4
@@ -181,6 +181,9 @@ SIGNATURES = {
     "dn_tape_free": (None, [_vp]),
     "dn_u8_normalize_flip": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "dn_flip_w": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "dn_nyu_prefilter": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dn_nyu_train_resample": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dn_nyu_val_resize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "dn_ubench_copy": (C.c_int, [_vp, _vp, _i64, _vp]),
     "dn_ubench_mfma_f32_flops": (_i64, [_i32, _i32]),
     "dn_ubench_mfma_f32": (C.c_int, [_vp, _i32, _i32, _vp]),

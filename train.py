@@ -12,6 +12,8 @@ What differs from the reference, on purpose:
     stay per replica exactly as under DataParallel;
   * Adam runs as one fused kernel over a flat arena; the 123.6 M unused VGG-classifier parameters are not optimised;
   * --unsupervised gets the 5-tuple loader the reference's branch needs (C-1); unknown selectors raise ValueError (C-12);
+  * `--dataset nyu` reads the reference's NYU Depth v2 .npy layout and runs its augmentation chain on the GPU (supervised_dispnet_amd/nyu.py,
+    always at the reference's 256x352 crop); it needs --with-gt and refuses --unsupervised and --shards;
   * `--synthetic N` (extension) trains on N synthetic samples with the statistics of SURVEY.md section 8d, for boxes
     without a dataset; tensorboard / progress-bar logging is replaced by plain prints and the two CSV logs.
 """
@@ -197,9 +199,22 @@ class Meter(object):
         return self.sum / max(self.count, 1)
 
 
+def check_dataset_args(args):
+    """Settings the NYU Depth v2 loader cannot serve, refused before anything touches the GPU (one line each)."""
+    if args.dataset != "nyu" or args.synthetic > 0:
+        return
+    if args.shards:
+        raise SystemExit("--shards is the KITTI scene-folder format; --dataset nyu reads DIR/nyu_depth_v2_other_resolution")
+    if args.unsupervised:
+        raise SystemExit("--dataset nyu has no --unsupervised branch: the reference's NYU loader yields (image, depth) pairs only")
+    if not args.with_gt:
+        raise SystemExit("--dataset nyu needs --with-gt: validation without ground truth cannot consume NYU batches")
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    check_dataset_args(args)
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -261,11 +276,23 @@ def main(argv=None):
         else:
             val_set = D.SequenceFolder(args.data, transform=D.Transform(mean, std, flip=False), seed=args.seed, train=False,
                                        sequence_length=args.sequence_length, with_refs=True)
+    elif args.dataset == "nyu":
+        train_set = val_set = None                   # NyuLoader reads DIR/nyu_depth_v2_other_resolution and augments on the GPU
+        if rank == 0:
+            print("=> NYU Depth v2: training crop 256x352 (the reference's), --img-height / --img-width do not apply")
     else:
-        raise ValueError("dataset '{}' needs the reference's NYU h5 loader, which is outside this path; use --synthetic".format(args.dataset))
+        raise ValueError("dataset '{}' is not supported on this path (kitti, nyu); use --synthetic".format(args.dataset))
     per_rank = args.batch_size // world
     workers = min(per_rank, os.cpu_count() or 1)     # the reference uses num_workers = batch_size and ignores -j (train.py:201-206)
-    if args.shards:
+    if train_set is None and args.dataset == "nyu":
+        from supervised_dispnet_amd.nyu import NyuLoader
+        train_loader = NyuLoader(args.data, per_rank, device, train=True, seed=args.seed, rank=rank, world=world)
+        train_sampler = train_loader                 # set_epoch() reshuffles and moves every sample to the epoch's draws
+        val_loader = NyuLoader(args.data, per_rank, device, train=False, rank=rank, world=world)
+        if rank == 0:
+            print("{} samples found in {} train scenes".format(len(train_loader.set), len(train_loader.set.scenes)))
+            print("{} samples found in {} valid scenes".format(len(val_loader.set), len(val_loader.set.scenes)))
+    elif args.shards:
         from supervised_dispnet_amd.shards import ShardLoader
         mean, std = D.normalization(args.imagenet_normalization, args.monodepth2)
         train_loader = ShardLoader(args.shards, per_rank, device, mean=mean, std=std, flip=True, shuffle=True, seed=args.seed, rank=rank,
@@ -278,10 +305,11 @@ def main(argv=None):
             print("{} samples found in {} train scenes".format(len(train_set), len(train_set.scenes)))
         train_sampler = D.RankSampler(len(train_set), args.batch_size, rank, world, shuffle=True, seed=args.seed)
         train_loader = torch.utils.data.DataLoader(train_set, batch_sampler=train_sampler, num_workers=workers, pin_memory=True)
-    if rank == 0:
-        print("{} samples found in {} valid scenes".format(len(val_set), len(val_set.scenes)))
-    val_sampler = D.RankSampler(len(val_set), args.batch_size, rank, world, shuffle=False, drop_last=False)
-    val_loader = torch.utils.data.DataLoader(val_set, batch_sampler=val_sampler, num_workers=workers, pin_memory=True)
+    if val_set is not None:
+        if rank == 0:
+            print("{} samples found in {} valid scenes".format(len(val_set), len(val_set.scenes)))
+        val_sampler = D.RankSampler(len(val_set), args.batch_size, rank, world, shuffle=False, drop_last=False)
+        val_loader = torch.utils.data.DataLoader(val_set, batch_sampler=val_sampler, num_workers=workers, pin_memory=True)
     if args.epoch_size == 0:
         args.epoch_size = len(train_loader)
 
