@@ -10,6 +10,14 @@ One rank per GPU (RCCL over xGMI); the only exchange is the bucketed gradient al
 Rank 0 prints ONE short JSON line on stdout (the contract fields, config and scalar summaries: emit()) and the full line below, with
 its per-kernel tables and nested configs, as `[bench-detail] {...}` on stderr.
 
+A plain run only sets up (build check, workload, launch tape and its bit-for-bit check), warms up, times --steps, writes --dump-outputs
+and prints the line.  Everything else it can measure runs after the timed steps with
+
+  --full            the fp32-matrix-instruction timing (`f32_mfma_path`), weak scaling at N > 1, the instrumented roofline steps
+                    (`roofline`, `roofline_hbm`, `step_*_frac`, measured peaks), `cpu_baseline`, the RCCL self-check at N > 1 and, for the
+                    default workload at N = 1, the nested runs of the other configs and batch sizes (`other_configs`, `strong_1gpu`).
+                    --alt-steps / --profile-steps / --extras / --rccl-selfcheck given explicitly still turn their part on or off alone.
+
   --dump-outputs DIR  after the timed steps: the last step's loss, a fixed sample of the parameters / gradients / Adam moments and the
                     BatchNorm buffers as DIR/<name>.npy (dump_outputs), for comparing two builds run with the same arguments.
 
@@ -23,7 +31,7 @@ its per-kernel tables and nested configs, as `[bench-detail] {...}` on stderr.
   --compute         f32x3 (default = the library's default) | f32 | bf16: arithmetic of the Winograd forward / input-gradient kernels.
                     f32x3 forms every fp32 product on the bf16 matrix cores from three exact bf16 pieces per operand (six partial
                     products, fp32 accumulation): an fp32 result -- error against fp64 at or below the fp32 instruction's
-                    (tests/test_gpu_kernels.py::test_winograd_error_vs_fp64, tools/ubench/bf16x3.hip); every default run also times the
+                    (tests/test_gpu_kernels.py::test_winograd_error_vs_fp64, tools/ubench/bf16x3.hip); every --full run also times the
                     same step with the fp32 matrix instruction (`f32_mfma_path`), so both numbers come from one run on one box.
 
   --launch          auto (default) | tape | eager | graph: how the host issues the step.  tape: the kernel launches and stream fences of ONE
@@ -36,7 +44,7 @@ its per-kernel tables and nested configs, as `[bench-detail] {...}` on stderr.
   --adam-overlap    auto (default) | 0 | 1: the Adam update of a gradient bucket right behind the bucket's completion / all-reduce, under
                     the rest of the backward pass (bit-identical to one update); auto = above 16 images per GPU.
 
-Besides the contract fields the line carries
+Besides the contract fields a --full line carries (a plain one has them as null)
   roofline      the dominant matrix-pipe kernel (by time).  `achieved` = multiply-accumulates the kernel EXECUTES on its matrix pipe x 2
                 divided by its launch durations (HIP events on the launch stream, instrumented steps after the timed region); `peak` =
                 the dense peak of THAT pipe (2500 TFLOP/s bf16 for the f32x3 / bf16 Winograd variants, which execute six / one bf16
@@ -348,20 +356,26 @@ def tape_host_profile(taped, dev):
             print("[tape-host-profile]    op %3d %8.1f us  %s" % (i, us, nm), file=sys.stderr)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also run every secondary measurement: f32_mfma_path, weak scaling at N > 1, "
+                         "the instrumented roofline steps, the CPU baseline, the RCCL self-check at N > 1 and (default workload, N = 1) the "
+                         "nested other_configs / strong_1gpu runs.  Without it a run only sets up, warms up, times --steps, writes "
+                         "--dump-outputs and prints the line")
     ap.add_argument("--config", default="vggbn128", choices=sorted(CONFIGS))
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="strong (default): --global-batch images per step over ALL ranks = BASELINE.json's 'b32 @1/2/4/8 GPU'; "
                          "weak: --batch images per rank")
     ap.add_argument("--global-batch", type=int, default=32, help="--scaling strong: images per step over ALL ranks")
     ap.add_argument("--batch", type=int, default=0, help="images per GPU per step (default: the config's; strong scaling: global/N)")
-    ap.add_argument("--profile-steps", type=int, default=2, help="instrumented steps (after the timed region) for the roofline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--per-layer", action="store_true", help="print the per-layer launch table to stderr")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="instrumented steps (after the timed region) for the roofline (default: 2 with --full or --per-layer, else 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--per-layer", action="store_true", help="print the per-layer launch table of the instrumented steps to stderr")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=6)
     ap.add_argument("--cpu-warmup", type=int, default=2)
@@ -369,12 +383,14 @@ def main():
                     help="arithmetic of the Winograd forward / input-gradient kernels (tensors and every other kernel are fp32 in all modes). "
                          "f32x3 (default, the library's default): fp32 products formed on the bf16 matrix cores from three exact bf16 pieces "
                          "per operand, fp32 accumulation -- error vs fp64 at or below the fp32 instruction's (tests/test_gpu_kernels.py); "
-                         "f32: the fp32 matrix instruction (also timed in every default run: field f32_mfma_path); "
+                         "f32: the fp32 matrix instruction (also timed in every --full run: field f32_mfma_path); "
                          "bf16: operands ROUNDED to bf16 (BASELINE configs[4]'s mixed precision; never the headline)")
-    ap.add_argument("--alt-steps", type=int, default=10, help="steps of the secondary timings (fp32 matrix instruction; weak scaling at N > 1) (0: skip)")
+    ap.add_argument("--alt-steps", type=int, default=None,
+                    help="steps of the secondary timings (fp32 matrix instruction; weak scaling at N > 1) (default: 10 with --full, else 0; 0: skip)")
     ap.add_argument("--rccl-selfcheck", default="auto", choices=["auto", "0", "1"],
                     help="N > 1: after the timed region, all-reduce one 20 MB bucket through this library's own RCCL communicator AND through "
-                         "torch.distributed and compare bitwise (config.rccl_selfcheck); guarded by a watchdog that prints the line anyway")
+                         "torch.distributed and compare bitwise (config.rccl_selfcheck); guarded by a watchdog that prints the line anyway "
+                         "(auto: with --full)")
     ap.add_argument("--graph", default="0", choices=["0", "1"],
                     help="1: replay the whole step (fwd + loss + bwd + Adam) as ONE captured hipGraph.  Off by default: measured on "
                          "ROCm 7.2 the replay is 1-4 %% SLOWER than the eager launches at every batch size (profiles/r02_strong_1gpu.txt)")
@@ -421,12 +437,21 @@ def main():
                     help="N = 1, default workload: after the headline's timed region, also time BASELINE configs[2..4] + the 480x640 VGG step "
                          "(10 steps each) and the 4 / 8 / 16-image steps of the metric's model (launch tape; + the data-parallel machinery on a "
                          "single-rank own-RCCL communicator), each as a nested run of this script, and carry them in the SAME line as "
-                         "`other_configs` / `strong_1gpu` (auto: on for the plain `python bench.py [--gpus 1]` call)")
+                         "`other_configs` / `strong_1gpu` (auto: on for the `python bench.py --full [--gpus 1]` call)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only plumbing check of the N>1 path: build the net, the arena, the buckets, one fake all-reduce cycle, tear down")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.profile_steps is None:
+        args.profile_steps = 2 if (args.full or args.per_layer) else 0
+    if args.alt_steps is None:
+        args.alt_steps = 10 if args.full else 0
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -733,9 +758,10 @@ def main():
 
     if world > 1:
         dist.barrier()
+    backend = os.environ.get("DN_DIST_BACKEND", "nccl")
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and args.config == "vggbn128":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == "vggbn128":
             cpu = cpu_baseline(H, W, args.cpu_batch, args.cpu_steps, args.cpu_warmup)
         total_images = batch * world * args.steps
         sec_step = dt / args.steps
@@ -749,7 +775,7 @@ def main():
                       "bf16": "bf16 multiply / f32 accumulate in the Winograd forward + input gradient; f32 tensors, f32 everywhere else"}[args.compute],
             "data": "synthetic",
             "config": {"workload": "%s, batch %d per GPU" % (desc, batch), "name": args.config, "global_batch": batch * world,
-                       "parallelism": "dp%d" % world, "final_loss": final_loss,
+                       "parallelism": "dp%d" % world, "final_loss": final_loss, "full": args.full,
                        "launch": ("one hipGraph replay per step" if graphed else
                                   ("launch tape: %d launches + %d stream fences (%d as the stop event of the launch in front) of one recorded step re-issued by dn_tape_replay, %d segment(s)"
                                    % (taped.launches, taped.fences, taped.riding_fences, taped.segments)) if taped is not None else "eager launches"),
@@ -765,8 +791,9 @@ def main():
                                                 if (world == 1 and reducer.comm is not None) else "")) if reducer is not None else "none (one rank)",
                        "comm_buckets": len(reducer.buckets) if reducer is not None else 0,
                        "comm_standin": standin,
-                       "rccl_selfcheck": {"status": "not run: " + ("one rank" if world == 1 else ("--rccl-selfcheck 0" if args.rccl_selfcheck == "0" else
-                                                                                                 "backend %s" % os.environ.get("DN_DIST_BACKEND", "nccl")))},
+                       "rccl_selfcheck": {"status": "not run: " + ("one rank" if world == 1 else
+                                                                   ("backend %s" % backend) if backend != "nccl" else
+                                                                   "--rccl-selfcheck 0" if args.rccl_selfcheck == "0" else "no --full")},
                        "dist_backend": dist.get_backend() if world > 1 else None},
             "step_tflops_credited_per_gpu": (step_credited_flops / sec_step / 1e12) if step_credited_flops else None,
             "step_credited_frac": (step_credited_flops / sec_step / 1e12 / PEAK_FP32_MFMA_TFLOPS) if step_credited_flops else None,
@@ -776,11 +803,11 @@ def main():
         }
     else:
         line = None
-    if world > 1 and args.rccl_selfcheck != "0" and os.environ.get("DN_DIST_BACKEND", "nccl") == "nccl":
+    if world > 1 and backend == "nccl" and (args.rccl_selfcheck == "1" or (args.rccl_selfcheck == "auto" and args.full)):
         rccl_selfcheck(line, dev, rank, world)
-    plain_call = (world == 1 and args.config == "vggbn128" and args.batch == 0 and args.launch == "auto" and args.reducer == "auto" and
-                  args.compute == "f32x3" and not args.no_cpu_baseline and "DN_BENCH_NESTED" not in os.environ)
-    if line is not None and (args.extras == "1" or (args.extras == "auto" and plain_call)):
+    full_call = (args.full and world == 1 and args.config == "vggbn128" and args.batch == 0 and args.launch == "auto" and args.reducer == "auto" and
+                 args.compute == "f32x3" and not args.no_cpu_baseline and "DN_BENCH_NESTED" not in os.environ)
+    if line is not None and (args.extras == "1" or (args.extras == "auto" and full_call)):
         line["other_configs"], line["strong_1gpu"] = run_extras(args)
     if watchdog is not None:
         watchdog.cancel()
@@ -815,7 +842,7 @@ def _nested(flags, timeout_s=420):
 
 
 def run_extras(args):
-    """What SURVEY.md section 8(d) / north_star ask beside the headline, timed by the SAME command the driver runs (round-5 verdict, item 3):
+    """What SURVEY.md section 8(d) / north_star ask beside the headline, timed by the same `bench.py --full` command (round-5 verdict, item 3):
     `other_configs` = BASELINE configs[2], [4], [3] and the 480 x 640 step of the metric's model, 10 timed steps each;
     `strong_1gpu`   = the metric's step at 4 / 8 / 16 images (what one GPU of an 8 / 4 / 2-GPU data-parallel run of the literal metric,
     global batch 32, would compute) through the launch tape, and the same with the data-parallel machinery live on a single-rank own-RCCL

@@ -85,3 +85,16 @@ def test_dump_outputs_keeps_a_small_arena_whole(tmp_path):
     bench.dump_outputs(str(tmp_path), loss, opt, nets)
     np.testing.assert_array_equal(np.load(tmp_path / "grads.npy"), opt.arena.flat_g.numpy())
     np.testing.assert_array_equal(np.load(tmp_path / "sample_index.npy"), np.arange(1000, dtype=np.float64))
+
+
+def test_plain_run_resolves_every_secondary_measurement_off_and_full_on():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs no secondary timing and no instrumented steps; --full restores the old
+    defaults; an explicit count or --per-layer still asks for its own part alone."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.alt_steps == 0 and plain.profile_steps == 0 and plain.steps == 7 and plain.warmup == 2
+    full = bench.parse_args(["--gpus", "1", "--full"])
+    assert full.full and full.alt_steps == 10 and full.profile_steps == 2
+    assert bench.parse_args(["--per-layer"]).profile_steps == 2
+    assert bench.parse_args(["--alt-steps", "3"]).alt_steps == 3
+    off = bench.parse_args(["--full", "--alt-steps", "0", "--profile-steps", "0"])
+    assert off.full and off.alt_steps == 0 and off.profile_steps == 0

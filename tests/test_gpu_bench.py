@@ -50,3 +50,26 @@ def test_bench_dump_outputs_is_the_last_step_and_repeats(tmp_path):
     assert np.load(tmp_path / "a" / "sample_index.npy").size == bench.DUMP_SAMPLE
     assert np.abs(np.load(tmp_path / "a" / "grads.npy")).max() > 0
 
+
+
+def _detail(flags):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + flags, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1, r.stdout[-2000:]
+    rows = [l for l in r.stderr.splitlines() if l.startswith("[bench-detail] ")]
+    assert len(rows) == 1, r.stderr[-2000:]
+    return json.loads(rows[0][len("[bench-detail] "):])
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_secondaries():
+    """Without --full the run times the headline only (no instrumented steps, no fp32-instruction timing, no CPU baseline, no nested
+    runs); --full brings the roofline and the fp32-instruction timing back into the same line."""
+    plain = _detail(["--steps", "2", "--warmup", "1", "--batch", "4"])
+    assert plain["config"]["full"] is False and plain["value"] > 0 and plain["steps"] == 2
+    for k in ("roofline", "roofline_hbm", "f32_mfma_path", "cpu_baseline", "step_executed_frac"):
+        assert plain[k] is None, k
+    assert "other_configs" not in plain and "strong_1gpu" not in plain
+    full = _detail(["--steps", "2", "--warmup", "1", "--batch", "4", "--full", "--alt-steps", "2", "--no-cpu-baseline"])
+    assert full["config"]["full"] is True and full["value"] > 0
+    assert full["roofline"]["achieved"] > 0 and full["roofline_hbm"]["achieved"] > 0
+    assert full["f32_mfma_path"]["value"] > 0 and full["step_executed_frac"] > 0

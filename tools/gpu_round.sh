@@ -4,8 +4,8 @@ tag=${1:-x}
 cfg=${2:-vggbn128}
 R=$(pwd)
 mkdir -p gpurun_out
-extra=""
-if [ "$cfg" != "vggbn128" ]; then extra="--no-cpu-baseline --alt-steps 0"; fi
+extra="--full"
+if [ "$cfg" != "vggbn128" ]; then extra="--full --no-cpu-baseline --alt-steps 0"; fi
 python bench.py --config $cfg --steps 10 --warmup 3 --per-layer $extra > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err
 cd /tmp; export TMPDIR=/tmp
 # per-kernel durations are taken single-stream (DN_WGRAD_STREAM=0), like the instrumented steps bench.py's roofline comes from:
