@@ -16,6 +16,14 @@ convolution's rounding: the forward's BatchNorm partial sums and their finalize 
 folded into the launch or not), the input gradient's BatchNorm-backward sums (partial rows, and the folded d(gamma), d(beta)), the
 bias gradient the weight-gradient call produces, and a disparity head's reciprocal (within 1 ulp of 1 / its own disparity).
 
+Any network (or several, run in one step: `audit(monkeypatch, net_a, net_b)`): calls are named by their module's name in
+named_modules(), the hot set is every nn.Conv2d / nn.ConvTranspose2d of the nets but the caller's exclusions, and a layer owes an
+input-gradient call exactly when one of its input pieces needs a gradient.  Reflection-padded layers (ConvLayer(reflect_pad=p)) are
+referenced over the reflected operand: the forward and weight gradient read the materialised input reflect-padded by p, the input
+gradient folds the padded border back (the adjoint of the reflection).  The fused DORN head (engine.block_ord_head) is checked as a
+whole: probabilities and decoded labels against the fp64 module sequence, and, through the closure it pushes on the tape, d(x),
+d(W), d(b) against fp64.
+
 Sampling: forward and input gradient reference the first, middle and last image in full (every border, every tile column, the
 blocks of the last round); the weight gradient reduces over all N images for SAMPLED_CIN input channels x all output channels x all
 taps.
@@ -32,6 +40,11 @@ U = 2.0 ** -24                 # unit round-off of fp32
 TINY = 2.0 ** -100             # absolute floor: far below any value these layers produce, far above fp64 round-off of zero
 REL_L2 = 5e-6                  # the suite's convention for an fp32 result against fp64 (tests/test_gpu_f32x3_fp64.py)
 SAMPLED_CIN = 8
+# the relative L2 criterion is taken against max(|ref|, |A| / COND_MAX): where the exact result cancels by more than COND_MAX (a
+# weight gradient in front of a BatchNorm, whose dy has zero mean per channel, reduced against all-positive ReLU / pool outputs:
+# |ref| ~ |A| / 200 measured), fp32's own rounding of the terms, <= u |A|, is no longer small against |ref| and the per-element
+# bound alone decides
+COND_MAX = 100.0
 
 # ------------------------------------------------------------------------------------------------------------- the bound
 # c of |got - ref| <= c * u * A.  A sums |terms| of the exact convolution, so an fp32 dot product of K terms in ANY order stays below
@@ -62,6 +75,8 @@ C_SUM = 130.0
 
 
 def family(kernel):
+    if kernel.startswith("dn::ord_head"):
+        return "ord_head"
     if kernel.startswith("dn::wino_wgrad"):
         return "wino_wgrad"
     if kernel.startswith("dn::wino_conv"):
@@ -78,19 +93,24 @@ def bound(kernel, pas, P=1):
     return C_WINO if fam == "wino" else C_DIRECT
 
 
-def compare(got, ref, A, c, act_slope=None, act_ulps=0.0):
+def compare(got, ref, A, c, act_slope=None, act_ulps=0.0, act_abs=None):
     """(ok, max err / (u A), relative L2, number of elements over the bound).  `act_slope` (per element) scales the bound of a
-    pre-activation error through the activation; `act_ulps` allows that many ulps of |ref| for the activation's own evaluation."""
+    pre-activation error through the activation; `act_ulps` allows that many ulps of |ref| for the activation's own evaluation;
+    `act_abs` (per element, in units of u) an absolute error of that evaluation that is not relative to |ref|."""
     got = got.double()
     err = (got - ref).abs()
     allow = c * U * A
     if act_slope is not None:
         allow = allow * act_slope
     allow = allow + act_ulps * U * ref.abs() + TINY
+    if act_abs is not None:
+        allow = allow + U * act_abs
     over = int((err > allow).sum()) + int((~torch.isfinite(got)).sum())
     scale = U * (A * (act_slope if act_slope is not None else 1.0)) + TINY
+    if act_abs is not None:
+        scale = scale + U * (act_abs + act_ulps * ref.abs()) / c
     worst = float((err / scale).max()) if err.numel() else 0.0
-    rel = float(err.norm() / (ref.norm() + 1e-300)) if err.numel() else 0.0
+    rel = float(err.norm() / (max(float(ref.norm()), float(A.norm()) / COND_MAX) + 1e-300)) if err.numel() else 0.0
     return over == 0 and rel <= REL_L2, worst, rel, over
 
 
@@ -165,26 +185,55 @@ def convT_nhwc(x, w, stride, pad, OH, OW):
     return conv_nhwc(z, w.flip(2, 3).transpose(0, 1), 1, R - 1 - pad, 1, OH, OW)
 
 
+def _reflect_index(n, p, device=None):
+    """Source row of each of the n + 2p rows of nn.ReflectionPad2d(p) over n rows: -i before row 0, 2(n-1) - i after row n-1."""
+    i = torch.arange(-p, n + p, device=device)
+    return torch.where(i < 0, -i, torch.where(i > n - 1, 2 * (n - 1) - i, i))
+
+
+def reflect_pad(x, p):
+    """x [n, H, W, C] reflection-padded by p on each side of H and W (the border row / column itself is not repeated)."""
+    return x[:, _reflect_index(x.shape[1], p, x.device)][:, :, _reflect_index(x.shape[2], p, x.device)]
+
+
+def reflect_fold(g, p):
+    """Adjoint of reflect_pad: g [n, H + 2p, W + 2p, C] -> [n, H, W, C], every padded row / column added to the one it copies."""
+    n, GH, GW, C = g.shape
+    H, W = GH - 2 * p, GW - 2 * p
+    rows = torch.zeros((n, H, GW, C), dtype=g.dtype, device=g.device).index_add_(1, _reflect_index(H, p, g.device), g)
+    return torch.zeros((n, H, W, C), dtype=g.dtype, device=g.device).index_add_(2, _reflect_index(W, p, g.device), rows)
+
+
 def fwd_ref(geo, X, W, bias):
-    """Pre-activation forward of one call on a materialised input X [n, IH, IW, Cin]."""
+    """Pre-activation forward of one call on a materialised input X [n, IH, IW, Cin] (reflection-padded first when geo["reflect"]:
+    then geo["pad"] is the reflection's width and the convolution itself has none)."""
+    pad = geo["pad"]
+    if geo.get("reflect"):
+        X, pad = reflect_pad(X, pad), 0
     if geo["transposed"]:
-        y = convT_nhwc(X, W, geo["stride"], geo["pad"], geo["OH"], geo["OW"])
+        y = convT_nhwc(X, W, geo["stride"], pad, geo["OH"], geo["OW"])
     else:
-        y = conv_nhwc(X, W, geo["stride"], geo["pad"], geo["dil"], geo["OH"], geo["OW"])
+        y = conv_nhwc(X, W, geo["stride"], pad, geo["dil"], geo["OH"], geo["OW"])
     return y + bias if bias is not None else y
 
 
 def dgrad_ref(geo, dY, W):
-    """Gradient w.r.t. the (materialised, concatenated) forward input [n, IH, IW, Cin] of one call."""
+    """Gradient w.r.t. the (materialised, concatenated) forward input [n, IH, IW, Cin] of one call (through the reflection when
+    geo["reflect"]: the gradient of the padded operand, its border folded back)."""
     if geo["transposed"]:
         return conv_nhwc(dY, W, geo["stride"], geo["pad"], 1, geo["IH"], geo["IW"])
     assert geo["dil"] == 1
+    if geo.get("reflect"):
+        p = geo["pad"]
+        return reflect_fold(convT_nhwc(dY, W, geo["stride"], 0, geo["IH"] + 2 * p, geo["IW"] + 2 * p), p)
     return convT_nhwc(dY, W, geo["stride"], geo["pad"], geo["IH"], geo["IW"])
 
 
 def wgrad_ref(geo, X, dY):
     """Weight gradient (framework layout) restricted to the input channels X holds: conv [Cout, c, R, S], convT [c, Cout, R, S]."""
     R, S, st, pad = geo["R"], geo["S"], geo["stride"], geo["pad"]
+    if geo.get("reflect"):
+        X, pad = reflect_pad(X, pad), 0
     c, Co = X.shape[-1], dY.shape[-1]
     if geo["transposed"]:
         out = torch.zeros((c, Co, R, S), dtype=X.dtype, device=X.device)
@@ -208,18 +257,23 @@ def fold_up(g):
 
 
 def activation(z, act, p0, p1):
-    """(value, slope bound) of the epilogue activation on fp64 pre-activations z."""
-    from supervised_dispnet_amd._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID_AFFINE
+    """(value, slope bound, ulps of |value|, absolute term in units of u) of the epilogue activation on fp64 pre-activations z."""
+    from supervised_dispnet_amd._lib import ACT_ELU, ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID_AFFINE
     if act == ACT_NONE:
-        return z, None, 0.0
+        return z, None, 0.0, None
     if act == ACT_RELU:
-        return z.clamp_min(0), None, 0.0
+        return z.clamp_min(0), None, 0.0, None
     if act == ACT_LEAKY:
-        return torch.where(z > 0, z, z * p0), None, 2.0
+        return torch.where(z > 0, z, z * p0), None, 2.0, None
     if act == ACT_SIGMOID_AFFINE:
         s = torch.sigmoid(z)
         # error of z propagates with slope p0 * s (1 - s); the activation's own exp / divide / FMA: a few ulps of the result
-        return p0 * s + p1, (p0 * s * (1 - s)).clamp_min(2.0 ** -30), 8.0
+        return p0 * s + p1, (p0 * s * (1 - s)).clamp_min(2.0 ** -30), 8.0, None
+    if act == ACT_ELU:
+        # expf(z) - 1 for z <= 0 (alpha 1, the kernels' form): slope exp(z) <= 1; expf is within 2 ulps of exp(z) (4 u exp(z)
+        # absolute) and the subtraction of 1 cancels, so that error is absolute, not relative to the result; + 1 ulp of the result
+        e = torch.exp(z.clamp_max(0))
+        return torch.where(z > 0, z, e - 1), torch.where(z > 0, torch.ones_like(z), e), 1.0, torch.where(z > 0, torch.zeros_like(z), 4 * e)
     raise NotImplementedError("activation %d" % act)
 
 
@@ -248,21 +302,26 @@ def capped_threads():
 
 # ------------------------------------------------------------------------------------------------------------ the audit
 class Audit(object):
-    def __init__(self, net, wgrad_channels=SAMPLED_CIN):
+    def __init__(self, nets, exclude=(), wgrad_channels=SAMPLED_CIN):
+        """`nets`: the networks one step runs; `exclude`: names of convolutions of theirs the step does not run through the three
+        wrapped entry points (e.g. DORN's conv_ord under the fused head).  With several nets a name is prefixed by its net's class."""
         from supervised_dispnet_amd import _lib, engine
         self.engine, self.lib = engine, _lib.load()
-        self.names = {}
-        mod_names = {id(m): n for n, m in net.named_modules()}
-        rt = net._runtime()
-        layers = []
-        for k, v in rt.items():
-            if k == "enc":
-                layers += [l for stage in v for l, _bn in stage]
-            else:
-                layers.append(v)
-        for l in layers:
-            self.names[id(l)] = mod_names[id(l.m)]
-        self.hot = sorted(self.names.values())
+        self.names = {}               # id(module) -> name
+        hot = []
+        for net in nets:
+            prefix = type(net).__name__ + ":" if len(nets) > 1 else ""
+            for n, m in net.named_modules():
+                if id(m) in self.names:
+                    continue
+                self.names[id(m)] = prefix + n
+                if isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d)):
+                    hot.append(prefix + n)
+        unknown = set(exclude) - set(hot)
+        if unknown:
+            raise KeyError("conv_audit: excluded layers that are no convolution of the nets: %s" % sorted(unknown))
+        self.hot = sorted(set(hot) - set(exclude))
+        self.needs_dx = {}            # layer -> whether a forward call read an input piece that needs a gradient
         self.rows = []
         self.failures = []
         self.pending = []             # forward BatchNorm statistics to check once their finalize has run
@@ -270,7 +329,7 @@ class Audit(object):
 
     # -- bookkeeping
     def _name(self, layer):
-        return self.names.get(id(layer), "?%s" % type(layer.m).__name__)
+        return self.names.get(id(layer.m), "?%s" % type(layer.m).__name__)
 
     def _row(self, name, pas, kernel, what, ok, worst, rel, over, geo=None, pieces=None, c=None):
         row = {"layer": name, "pass": pas, "kernel": kernel, "what": what, "ok": ok, "worst": worst, "rel": rel, "over": over, "c": c,
@@ -282,7 +341,7 @@ class Audit(object):
     @staticmethod
     def _geo(layer, N, IH, IW, OH, OW):
         return {"N": N, "IH": IH, "IW": IW, "OH": OH, "OW": OW, "R": layer.R, "S": layer.S, "stride": layer.stride, "pad": layer.pad,
-                "dil": layer.dil, "transposed": layer.transposed, "Cin": layer.Cin, "Cout": layer.Cout}
+                "dil": layer.dil, "transposed": layer.transposed, "reflect": layer.reflect, "Cin": layer.Cin, "Cout": layer.Cout}
 
     def _kernel(self):
         return self.lib.dn_last_kernel().decode(errors="replace")
@@ -389,14 +448,29 @@ class Audit(object):
         self._row(name, "dgrad", kernel, "bn_bwd_sums%s" % ("(folded)" if final is not None else ""), ok, max(r[1] for r in res),
                   max(r[2] for r in res), sum(r[3] for r in res), c=C_SUM)
 
+    def _check_partial_sum_preact(self, name, kernel, partial, pieces, geo, Wt):
+        """The partial rows of a layer with an epilogue activation (Disp_res_50's conv1: the statistics of a BatchNorm the
+        reference computes from the pre-activation and discards) sum the pre-bias, pre-activation result, which the kernel does
+        not store: against the fp64 convolution of all images, with the convolution's bound + the sum's."""
+        ref = A = 0
+        for i0 in range(0, geo["N"], 4):
+            X, Xm = self._operands(pieces, images=list(range(i0, min(geo["N"], i0 + 4))))
+            z = fwd_ref(geo, X, Wt, None)
+            ref = ref + z.reshape(-1, z.shape[-1]).sum(0)
+            A = A + fwd_ref(geo, Xm, Wt.abs(), None).reshape(-1, z.shape[-1]).sum(0)
+        c = C_DIRECT + C_SUM
+        ok, worst, rel, over = compare(partial[..., 0].double().sum(0), ref, A, c)
+        self._row(name, "fwd", kernel, "bn_partial_sum(pre-act)", over == 0, worst, rel, over, c=c)
+
     # -- the three wrapped entry points
     def conv_forward(self, orig, *args, **kwargs):
         ba = inspect.signature(orig).bind(*args, **kwargs)
         ba.apply_defaults()
         A_ = ba.arguments
+        from supervised_dispnet_amd._lib import ACT_NONE as ACT_NONE_
         layer, pieces, act, p0, p1 = A_["layer"], A_["pieces"], A_["act"], A_["p0"], A_["p1"]
-        if A_["out_view"] is not None or layer.reflect:
-            raise NotImplementedError("conv_audit: out_view / reflection padding are not audited")
+        if A_["out_view"] is not None:
+            raise NotImplementedError("conv_audit: out_view is not audited")
         self.flush()
         torch.cuda.synchronize()
         a0 = pieces[0].act
@@ -418,12 +492,15 @@ class Audit(object):
         b = layer.m.bias.detach().double() if layer.m.bias is not None else None
         z = fwd_ref(geo, X, Wt, b)
         Az = fwd_ref(geo, Xm, Wt.abs(), b.abs() if b is not None else None)
-        ref, slope, ulps = activation(z, act, p0, p1)
+        ref, slope, ulps, absu = activation(z, act, p0, p1)
         c = bound(kernel, "fwd")
-        ok, worst, rel, over = compare(y[imgs], ref, Az, c, slope, ulps)
+        ok, worst, rel, over = compare(y[imgs], ref, Az, c, slope, ulps, absu)
+        self.needs_dx[name] = self.needs_dx.get(name, False) or any(p.act.needs_grad for p in pieces)
         self._row(name, "fwd", kernel, "y", ok, worst, rel, over, geo, [(p.act.C, p.up, p.act.scale is not None) for p in pieces], c)
-        if partial is not None:
+        if partial is not None and act == ACT_NONE_:
             self._check_partial_sum(name, kernel, partial, y, layer.m.bias.detach() if layer.m.bias is not None else None)
+        elif partial is not None:
+            self._check_partial_sum_preact(name, kernel, partial, pieces, geo, Wt)
         if bn is not None:
             fold = A_["bn_fold"]
             self.pending.append({"name": name, "kernel": kernel, "y": y, "bn": bn, "rm0": rm0, "rv0": rv0, "mean": fold[1],
@@ -520,10 +597,134 @@ class Audit(object):
                 self._row(name, "wgrad", "dn::colreduce_kernel", "db", ok, worst, rel, over, c=C_SUM)
         return dw
 
+    # -- the fused DORN head
+    def block_ord_head(self, orig, tape, sink, x, conv, mask):
+        """Forward: probabilities and decoded labels of the sampled images against the fp64 module sequence (mask, 1 x 1 conv,
+        clamp to [1e-8, 1e8], pair softmax); backward (the closure the block pushes on the tape, wrapped): d(x) of the sampled
+        images, d(W) and d(b) over all N H W pixels."""
+        self.flush()
+        torch.cuda.synchronize()
+        K = conv.out_channels // 2
+        name = self.names.get(id(conv), "?ord_head")
+
+        class _Tape(object):
+            def push(_self, fn, out=None):
+                tape.push(lambda: self._ord_head_bwd(fn, name, x, conv, mask, o, K, sink), out)
+
+        o, d = orig(_Tape(), sink, x, conv, mask)
+        torch.cuda.synchronize()
+        imgs = sample_images(x.N)
+        P, allow, _, _ = self._ord_head_ref(x, conv, mask, imgs)
+        inexact = allow > TINY
+        got = o.t[imgs].permute(0, 2, 3, 1)
+        # c: the 16-term dot product + bias of a logit in fp32 in any order is within 16 u A of exact (C_DIRECT >= 16 covers the
+        # worst case, not only the statistical one); the clamp is 1-Lipschitz; the pair softmax sigmoid(b - a) passes an error of
+        # (a, b) on with slope P (1 - P); its exp and divide: a few ulps of P
+        ok, worst, rel, over = compare(got, P[0], P[1], C_DIRECT, P[2], 8.0 * inexact.double())
+        self._row(name, "fwd", "dn::ord_head_fwd_kernel", "P", ok, worst, rel, over, c=C_DIRECT)
+        # decoded label = #{k: P_k > 0.5}: exact wherever no P of the pixel lies within its bound of 0.5
+        dec_ref = (P[0] > 0.5).sum(-1)
+        amb = (((P[0] - 0.5).abs() <= allow) & inexact).any(-1)
+        bad = (d.t[imgs, 0].to(dec_ref.device) != dec_ref) & ~amb
+        nbad = int(bad.sum())
+        self._row(name, "fwd", "dn::ord_head_fwd_kernel", "decode(%d amb)" % int(amb.sum()), nbad == 0, 0.0, 0.0, nbad, c=0.0)
+        return o, d
+
+    def _ord_head_ref(self, x, conv, mask, imgs):
+        """fp64 ((P, A of P's logits, slope), |P - ref| allowance, logits z, their A) of images `imgs`, NHWC / [..., 2K]."""
+        xm = nhwc_view(x)[imgs].double()
+        if mask is not None:
+            xm = xm * mask[imgs].double()[:, None, None, :]
+        Wt = conv.weight.detach().double().reshape(conv.out_channels, -1)
+        b = conv.bias.detach().double()
+        z = xm @ Wt.t() + b
+        Az = xm.abs() @ Wt.abs().t() + b.abs()
+        a_, b_ = z[..., 0::2].clamp(1e-8, 1e8), z[..., 1::2].clamp(1e-8, 1e8)
+        P = torch.sigmoid(b_ - a_)
+        # a logit further than its bound below 1e-8 is clamped exactly, whatever its error: it adds nothing to the error of b - a;
+        # a pair clamped on both sides has b - a = 0 and P = 1 / (1 + exp(0)) = 0.5 exactly (allowance 0)
+        live_a = z[..., 0::2] > 1e-8 - C_DIRECT * U * Az[..., 0::2]
+        live_b = z[..., 1::2] > 1e-8 - C_DIRECT * U * Az[..., 1::2]
+        A = Az[..., 0::2] * live_a + Az[..., 1::2] * live_b
+        slope = (P * (1 - P)).clamp_min(2.0 ** -30)
+        allow = (C_DIRECT * U * A * slope + 8.0 * U * P) * (live_a | live_b) + TINY
+        return (P, A, slope), allow, z, Az
+
+    def _ord_head_bwd(self, fn, name, x, conv, mask, o, K, sink):
+        if o.grad is None:
+            return fn()
+        self.flush()
+        torch.cuda.synchronize()
+        N = x.N
+        imgs = sample_images(N)
+        G = o.grad.double()                                   # [N, K, H, W] planar
+        before = x.grad[imgs].double().clone() if (x.needs_grad and x.grad is not None) else None
+        fn()
+        torch.cuda.synchronize()
+        kern = "dn::ord_head_bwd_kernel"
+        dW = dB = AW = AB = None
+        dx_ref = dx_A = None
+        for n in range(N):
+            (P, _A, _s), allow, z, Az = self._ord_head_ref(x, conv, mask, [n])
+            g = G[n:n + 1].permute(0, 2, 3, 1)                # [1, H, W, K]
+            s = P * (1 - P)
+            live_a = (z[..., 0::2] > 1e-8) & (z[..., 0::2] < 1e8)
+            live_b = (z[..., 1::2] > 1e-8) & (z[..., 1::2] < 1e8)
+            dz = torch.zeros_like(z)
+            dz[..., 0::2] = -g * s * live_a
+            dz[..., 1::2] = g * s * live_b
+            # what the kernel's dz may be off by, in units of u: its recomputed P carries the forward's error (allow) into
+            # s = P (1 - P) with slope |1 - 2P|, + a few ulps of its own products; a logit within its bound of the clamp's edge may
+            # take either side of it (then the whole term)
+            e = g.abs() * ((1 - 2 * P).abs() * allow / U + 4 * s)
+            za, zb = z[..., 0::2], z[..., 1::2]
+            tol_a, tol_b = C_DIRECT * U * Az[..., 0::2] + TINY, C_DIRECT * U * Az[..., 1::2] + TINY
+            amb_a = ((za - 1e-8).abs() <= tol_a) | ((za - 1e8).abs() <= tol_a)
+            amb_b = ((zb - 1e-8).abs() <= tol_b) | ((zb - 1e8).abs() <= tol_b)
+            edz = torch.zeros_like(z)
+            edz[..., 0::2] = e + amb_a * (g * s).abs() / U
+            edz[..., 1::2] = e + amb_b * (g * s).abs() / U
+            xm = nhwc_view(x)[n:n + 1].double()
+            mk = mask[n].double() if mask is not None else None
+            if mk is not None:
+                xm = xm * mk
+            dz2, edz2, xm2 = dz.reshape(-1, 2 * K), edz.reshape(-1, 2 * K), xm.reshape(-1, xm.shape[-1])
+            Wt = conv.weight.detach().double().reshape(2 * K, -1)
+            w_ = dz2.t() @ xm2
+            aw = dz2.abs().t() @ xm2.abs() + (edz2.t() @ xm2.abs()) / (C_WGRAD_RUN + math.log2(N * x.H * x.W))
+            b_, ab = dz2.sum(0), dz2.abs().sum(0) + edz2.sum(0) / (C_WGRAD_RUN + math.log2(N * x.H * x.W))
+            dW, AW = (w_, aw) if dW is None else (dW + w_, AW + aw)
+            dB, AB = (b_, ab) if dB is None else (dB + b_, AB + ab)
+            if n in imgs:
+                r = dz2 @ Wt
+                ar = dz2.abs() @ Wt.abs() + (edz2 @ Wt.abs()) / C_DIRECT
+                if mk is not None:
+                    r, ar = r * mk, ar * mk.abs()
+                dx_ref = r if dx_ref is None else torch.cat([dx_ref, r])
+                dx_A = ar if dx_A is None else torch.cat([dx_A, ar])
+        if x.needs_grad:
+            got = x.grad[imgs].double().reshape(-1, x.C)
+            if before is not None:
+                got = got - before.reshape(-1, x.C)
+                dx_A = dx_A + before.reshape(-1, x.C).abs()
+            # dx: a 2K-term sum per element, c as for a direct kernel
+            ok, worst, rel, over = compare(got, dx_ref, dx_A, C_DIRECT)
+            self._row(name, "dgrad", kern, "head_dx", ok, worst, rel, over, c=C_DIRECT)
+        P_ = N * x.H * x.W
+        c = C_WGRAD_RUN + math.log2(max(P_, 2))
+        dw = sink.get(conv.weight)
+        dw = dw if dw is not None else sink.dest(conv.weight)
+        db = sink.get(conv.bias)
+        db = db if db is not None else sink.dest(conv.bias)
+        ok, worst, rel, over = compare(dw.reshape(2 * K, -1), dW, AW, c)
+        self._row(name, "wgrad", kern, "head_dw", ok, worst, rel, over, c=c)
+        ok, worst, rel, over = compare(db, dB, AB, c)
+        self._row(name, "wgrad", kern, "head_db", ok, worst, rel, over, c=c)
+
     # -- results
     def coverage(self, training):
         """Per pass, the hot layers whose calls were audited a wrong number of times: {} when every call was seen exactly once (a
-        layer's input gradient only where its input needs one: every layer but the first)."""
+        layer's input gradient only where one of its input pieces needs a gradient: not the stems, which read the images)."""
         counts = {}
         for r in self.rows:
             if r["what"] in ("y", "dx", "dw"):
@@ -534,7 +735,7 @@ class Audit(object):
         for pas in passes:
             seen = counts.get(pas, {})
             for n in self.hot:
-                want = 0 if (pas == "dgrad" and n == "features.features.0") else 1
+                want = 0 if (pas == "dgrad" and not self.needs_dx.get(n, True)) else 1
                 if seen.get(n, 0) != want:
                     bad.setdefault(pas, {})[n] = seen.get(n, 0)
             for n in seen:
@@ -555,17 +756,18 @@ class Audit(object):
     def worst_by_family(self):
         out = {}
         for r in self.rows:
-            if r["what"] in ("y", "dx", "dw"):
+            if r["what"] in ("y", "dx", "dw", "P", "head_dx", "head_dw", "head_db"):
                 k = (family(r["kernel"]), r["pass"])
                 out[k] = max(out.get(k, 0.0), r["worst"])
         return out
 
 
-def audit(monkeypatch, net, **kw):
-    """Install the wrappers for the rest of the test (monkeypatch undoes them); returns the Audit collecting the rows."""
+def audit(monkeypatch, *nets, **kw):
+    """Install the wrappers for the rest of the test (monkeypatch undoes them); returns the Audit collecting the rows.
+    `exclude=(names...)`: convolutions of the nets that do not run through the wrapped entry points."""
     from supervised_dispnet_amd import engine
-    a = Audit(net, **kw)
-    for fn in ("conv_forward", "conv_dgrad", "conv_wgrad"):
+    a = Audit(nets, **kw)
+    for fn in ("conv_forward", "conv_dgrad", "conv_wgrad", "block_ord_head"):
         orig = getattr(engine, fn)
         method = getattr(a, fn)
         monkeypatch.setattr(engine, fn, (lambda o, m: (lambda *args, **kwargs: m(o, *args, **kwargs)))(orig, method))
