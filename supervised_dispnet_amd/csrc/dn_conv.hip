@@ -21,9 +21,6 @@ namespace dn {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef DN_STAGGER
-#define DN_STAGGER 0
-#endif
 constexpr int LDK = 36;  // padded LDS row (floats) of a [rows][32] K-chunk tile
 
 __device__ __forceinline__ float apply_act(float v, int act, float p0, float p1) {
@@ -34,33 +31,6 @@ __device__ __forceinline__ float apply_act(float v, int act, float p0, float p1)
     case DN_ACT_SIGMOID_AFFINE: return p0 / (1.f + expf(-v)) + p1;
     default: return v;
   }
-}
-
-// floor(n/d), n < 2^31, with magic M = floor(2^32/d) (0xFFFFFFFF for d == 1): estimate is exact or one low; branch-free fix-up
-__device__ __forceinline__ unsigned fastdiv(unsigned n, unsigned d, unsigned M, unsigned* rem) {
-  unsigned q = __umulhi(n, M);
-  unsigned r = n - q * d;
-  const bool fix = r >= d;
-  q += fix ? 1u : 0u;
-  r -= fix ? d : 0u;
-  *rem = r;
-  return q;
-}
-
-// Two blocks share a CU, i.e. two waves share each SIMD's matrix pipe.  Launched together they run IN PHASE (both in their MFMA
-// phase, then both staging: pipe idle ~25 % -- measured SQ_VALU_MFMA_BUSY 66 %).  A static priority asymmetry between the
-// two wave slots of a SIMD breaks the symmetry: the favoured wave keeps the pipe whenever it wants it, the other fills the
-// gaps while the first one stages.  HW_REG_HW_ID (id 4) bits [3:0] = wave slot within the SIMD.
-__device__ __forceinline__ void stagger_priority() {
-  const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-  const unsigned slot = (lin >> 8) & 1u;
-#if DN_STAGGER == 2
-  if (slot & 1u) {
-    __builtin_amdgcn_s_sleep(64);   // ~4k cycles: start the odd slot half a chunk late
-  }
-#else
-  if (slot & 1u) __builtin_amdgcn_s_setprio(2);
-#endif
 }
 
 // ReflectionPad2d index map for v in [-(n-1), 2(n-1)]
@@ -295,7 +265,6 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_kernel(const IgemmParams p)
   int* taps = reinterpret_cast<int*>(Bs + 2 * BN * LDK);   // [kMaxTaps]  (dy | dx<<16)
   int* rowpix = taps + kMaxTaps;                           // [BM] output pixel index or -1
 
-  if (DN_STAGGER) stagger_priority();
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
@@ -309,8 +278,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_kernel(const IgemmParams p)
     int m = m0 + r, pix = -1;
     if (m < p.M) {
       unsigned gx, gy;
-      const unsigned t = fastdiv((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
-      const int n = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+      const unsigned t = fastdiv_dev((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
+      const int n = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
       int oy = (int)gy * p.osy + ph.ooy, ox = (int)gx * p.osx + ph.oox;
       if (oy < p.OH && ox < p.OW) pix = (n * p.OH + oy) * p.OW + ox;
     }
@@ -325,8 +294,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_kernel(const IgemmParams p)
     int m = m0 + r0 + 32 * i;
     if (m < p.M) {
       unsigned gx, gy;
-      const unsigned t = fastdiv((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
-      rn[i] = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+      const unsigned t = fastdiv_dev((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
+      rn[i] = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
       rby[i] = (int)gy * p.sy;
       rbx[i] = (int)gx * p.sx;
     } else {
@@ -361,7 +330,7 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_kernel(const IgemmParams p)
     const int kl = kcl * kChunk + g * 4;
     if constexpr (ALLVEC) {
       unsigned c;
-      const int j = (int)fastdiv((unsigned)kl, (unsigned)S.C, S.mC, &c);
+      const int j = (int)fastdiv_dev((unsigned)kl, (unsigned)S.C, S.mC, &c);
       const bool kvalid = j < ntaps;
       const int t = taps[kvalid ? j : 0];
       const int dy = (int)(short)(t & 0xffff), dx = t >> 16;
@@ -531,8 +500,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_u32_kernel(const IgemmParam
     int m = m0 + r, pix = -1;
     if (m < p.M) {
       unsigned gx, gy;
-      const unsigned t = fastdiv((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
-      const int n = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+      const unsigned t = fastdiv_dev((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
+      const int n = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
       int oy = (int)gy * p.osy + ph.ooy, ox = (int)gx * p.osx + ph.oox;
       if (oy < p.OH && ox < p.OW) pix = (n * p.OH + oy) * p.OW + ox;
     }
@@ -546,8 +515,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_u32_kernel(const IgemmParam
   auto row_coords = [&](int i, int* n, int* by, int* bx) {
     const int m = m0 + r0 + 32 * i;
     unsigned gx, gy;
-    const unsigned t = fastdiv(m < p.M ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
-    *n = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+    const unsigned t = fastdiv_dev(m < p.M ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
+    *n = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
     *by = (int)gy * p.sy;
     *bx = (int)gx * p.sx;
   };
@@ -752,8 +721,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_u32_kernel(const IgemmParam
       {
         const int m = m0 + prow;
         unsigned gx, gy;
-        const unsigned t = fastdiv(m < p.M ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
-        pn = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+        const unsigned t = fastdiv_dev(m < p.M ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
+        pn = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
         pby = (int)gy * p.sy;
         pbx = (int)gx * p.sx;
       }
@@ -768,7 +737,7 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_u32_kernel(const IgemmParam
           for (int e = 0; e < KPT; ++e) {
             const int k = cl * kChunk + pk0 + e;
             unsigned c;
-            const int j = (int)fastdiv((unsigned)k, (unsigned)S.C, S.mC, &c);
+            const int j = (int)fastdiv_dev((unsigned)k, (unsigned)S.C, S.mC, &c);
             float v = 0.f;
             if (j < ntaps) {
               const int tp = taps[j];
@@ -899,8 +868,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_x3_kernel(const IgemmParams
     int m = m0 + r, pix = -1;
     if (m < p.M) {
       unsigned gx, gy;
-      const unsigned t = fastdiv((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
-      const int n = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+      const unsigned t = fastdiv_dev((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
+      const int n = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
       int oy = (int)gy * p.osy + ph.ooy, ox = (int)gx * p.osx + ph.oox;
       if (oy < p.OH && ox < p.OW) pix = (n * p.OH + oy) * p.OW + ox;
     }
@@ -914,8 +883,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_x3_kernel(const IgemmParams
   auto row_coords = [&](int i, int* n, int* by, int* bx) {
     const int m = m0 + r0 + 32 * i;
     unsigned gx, gy;
-    const unsigned t = fastdiv(m < p.M ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
-    *n = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+    const unsigned t = fastdiv_dev(m < p.M ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
+    *n = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
     *by = (int)gy * p.sy;
     *bx = (int)gx * p.sx;
   };
@@ -1164,8 +1133,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_x3_kernel(const IgemmParams
       {
         const int m = m0 + prow;
         unsigned gx, gy;
-        const unsigned t = fastdiv(m < p.M ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
-        pn = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+        const unsigned t = fastdiv_dev(m < p.M ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
+        pn = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
         pby = (int)gy * p.sy;
         pbx = (int)gx * p.sx;
       }
@@ -1180,7 +1149,7 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_x3_kernel(const IgemmParams
           for (int e = 0; e < KPT; ++e) {
             const int k = cl * kChunk + pk0 + e;
             unsigned c;
-            const int j = (int)fastdiv((unsigned)k, (unsigned)S.C, S.mC, &c);
+            const int j = (int)fastdiv_dev((unsigned)k, (unsigned)S.C, S.mC, &c);
             float v = 0.f;
             if (j < ntaps) {
               const int tp = taps[j];
@@ -1337,8 +1306,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_x3b_kernel(const IgemmParam
     int m = m0 + r, pix = -1;
     if (m < p.M) {
       unsigned gx, gy;
-      const unsigned t = fastdiv((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
-      const int n = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+      const unsigned t = fastdiv_dev((unsigned)m, (unsigned)p.GW, p.mGW, &gx);
+      const int n = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
       const int oy = (int)gy * p.osy + ph.ooy, ox = (int)gx * p.osx + ph.oox;
       if (oy < p.OH && ox < p.OW) pix = (n * p.OH + oy) * p.OW + ox;
     }
@@ -1353,8 +1322,8 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_x3b_kernel(const IgemmParam
     const int m = m0 + r0 + 32 * i;
     rvalid[i] = m < p.M;
     unsigned gx, gy;
-    const unsigned t = fastdiv(rvalid[i] ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
-    const int n = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+    const unsigned t = fastdiv_dev(rvalid[i] ? (unsigned)m : 0u, (unsigned)p.GW, p.mGW, &gx);
+    const int n = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
     rby[i] = (int)gy * p.sy;
     rbx[i] = (int)gx * p.sx;
     rbase[i] = n * (int)S.sn + 4 * g;
@@ -1580,7 +1549,6 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_kernel(const IgemmParams p
   float* Xs = smem + 2 * 32 * BNW;                         // [2][32][BKW]
   int* taps = reinterpret_cast<int*>(Xs + 2 * 32 * BKW);   // [kMaxTaps]
 
-  if (DN_STAGGER) stagger_priority();
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave / WAVES_K, wk = wave % WAVES_K;
   const int kt = blockIdx.x, n0 = blockIdx.y * BNW;
@@ -1644,8 +1612,8 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_kernel(const IgemmParams p
     if constexpr (ALLVEC) {
       unsigned gx, gy;
       const unsigned mm = rowvalid ? (unsigned)m : 0u;
-      const unsigned t = fastdiv(mm, (unsigned)p.GW, p.mGW, &gx);
-      const int n = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+      const unsigned t = fastdiv_dev(mm, (unsigned)p.GW, p.mGW, &gx);
+      const int n = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
       const int by = (int)gy * p.sy, bx = (int)gx * p.sx;
       const int grow = (int)mm * p.Ntot + n0 + g * 4;
 #pragma unroll
@@ -1855,7 +1823,7 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_u32_kernel(const IgemmPara
     any_scalar = any_scalar || qscal[q];
     {
       unsigned c;
-      const int j = (int)fastdiv((unsigned)(kcl * kChunk + g * 4), (unsigned)S.C, S.mC, &c);
+      const int j = (int)fastdiv_dev((unsigned)(kcl * kChunk + g * 4), (unsigned)S.C, S.mC, &c);
       const bool ok = qvec[q] && j < ntaps;
       const int jj = ok ? j : 0;
       qtap[q] = ok ? (((int)p.tdy[jj] & 0xffff) | ((int)p.tdx[jj] << 16)) : (int)0x80008000;
@@ -1875,7 +1843,7 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_u32_kernel(const IgemmPara
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       unsigned c;
-      const int j = (int)fastdiv((unsigned)(kcl * kChunk + g2 * 4 + e), (unsigned)S.C, S.mC, &c);
+      const int j = (int)fastdiv_dev((unsigned)(kcl * kChunk + g2 * 4 + e), (unsigned)S.C, S.mC, &c);
       const bool ok = qscal[q] && j < ntaps;
       const int jj = ok ? j : 0;
       qst[q][e] = ok ? (((int)p.tdy[jj] & 0xff) | (((int)p.tdx[jj] & 0xff) << 8) | ((int)c << 16)) : -1;
@@ -1901,16 +1869,16 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_u32_kernel(const IgemmPara
     rowvalid = m < m_end;
     const unsigned mm = rowvalid ? (unsigned)m : 0u;
     unsigned gx, gy;
-    const unsigned t = fastdiv(mm, (unsigned)p.GW, p.mGW, &gx);
-    pn = (int)fastdiv(t, (unsigned)p.GH, p.mGH, &gy);
+    const unsigned t = fastdiv_dev(mm, (unsigned)p.GW, p.mGW, &gx);
+    pn = (int)fastdiv_dev(t, (unsigned)p.GH, p.mGH, &gy);
     pby = (int)gy * p.sy;
     pbx = (int)gx * p.sx;
     goffB = (mm * (unsigned)p.Ntot + (unsigned)(n0 + g * 4)) * 4u;
     if (any_scalar) {
       const int m2 = mbase + r2;
       rowvalid2 = m2 < m_end;
-      const unsigned t2 = fastdiv(rowvalid2 ? (unsigned)m2 : 0u, (unsigned)p.GW, p.mGW, &gx);
-      pn2 = (int)fastdiv(t2, (unsigned)p.GH, p.mGH, &gy);
+      const unsigned t2 = fastdiv_dev(rowvalid2 ? (unsigned)m2 : 0u, (unsigned)p.GW, p.mGW, &gx);
+      pn2 = (int)fastdiv_dev(t2, (unsigned)p.GH, p.mGH, &gy);
       pby2 = (int)gy * p.sy;
       pbx2 = (int)gx * p.sx;
     }
@@ -2150,8 +2118,7 @@ static int enable_big_lds(K kernel, size_t bytes) {
 
 template <int BM, int BN, int WM, int WN, bool ALLVEC>
 static int launch_conv_v(const IgemmParams& p, hipStream_t stream) {
-  size_t lds = (size_t)(2 * BM * LDK + 2 * BN * LDK) * sizeof(float) + (kMaxTaps + BM) * sizeof(int);
-  lds += (size_t)0;   // tuning aid: lowers blocks per CU
+  const size_t lds = (size_t)(2 * BM * LDK + 2 * BN * LDK) * sizeof(float) + (kMaxTaps + BM) * sizeof(int);
   auto kernel = igemm_conv_kernel<BM, BN, WM, WN, ALLVEC>;
   int rc = enable_big_lds(kernel, lds);
   if (rc != DN_OK) return rc;
@@ -2199,7 +2166,7 @@ static size_t x3_splitk_workspace_bytes(int blocks, int ks, int tiles_per_wave) 
   return kX3SplitKCounterBytes + (size_t)blocks * ks * tiles_per_wave * 4 * 256 * sizeof(float) * 4;
 }
 
-// upper bound over the tile shapes run_conv may pick (64-row tiles give the most blocks; two 32 x 32 tiles per wave at most)
+// upper bound over the tile shapes launch_tiled_conv may pick (64-row tiles give the most blocks; two 32 x 32 tiles per wave at most)
 size_t conv_x3_splitk_workspace_upper_bytes(const IgemmParams& p) {
   if (p.compute != DN_COMPUTE_F32X3 || !p.uni32 || p.BN < 64) return 0;
   const int tiles = ((p.M + 63) / 64) * (p.Npad / p.BN);
@@ -2259,9 +2226,34 @@ static int launch_conv_x3b(const IgemmParams& p, hipStream_t stream) {
 
 template <int BM, int BN, int WM, int WN>
 static int launch_conv(const IgemmParams& p, hipStream_t stream) {
-  if (p.uni32 && !false)
+  if (p.uni32)
     return launch_conv_u32<BM, BN, WM, WN>(p, stream);
   return p.allvec ? launch_conv_v<BM, BN, WM, WN, true>(p, stream) : launch_conv_v<BM, BN, WM, WN, false>(p, stream);
+}
+
+// The tiled kernels: every layer no other family of run_conv takes.  Picks the tile shape.
+static int launch_tiled_conv(const IgemmParams& p, hipStream_t s) {
+  // Few row tiles (the 4x13 / 8x26 decoder levels at b32: 13-52 tiles of 128 rows) leave most of the 256 CUs without a block;
+  // 64-row tiles double the block count at the same per-wave MFMA density along N.  Not with batch statistics: the
+  // bn_partial layout is per 128-row tile.
+  const long long blocks128 = (long long)((p.M + 127) / 128) * (p.Npad / p.BN) * p.nphases;
+  const bool small_m = p.uni32 && p.bn_partial == nullptr && blocks128 <= 208;
+  if (p.compute == DN_COMPUTE_F32X3 && p.uni32 && !knobs().no_x3_direct && p.BN >= 64) {
+    // (the 32-wide N tile -- one 32 x 32 tile per wave, 12 matrix instructions per chunk against five split-and-store items -- measured
+    //  4-17 % slower than the fp32 instruction: it stays on that)
+    // fp32 products on the bf16 matrix cores (wave tiles of at most 2 x 32 x 32: the 128-wide N tile runs as 64-row blocks)
+    if (conv_x3b_eligible(p)) return launch_conv_x3b(p, s);       // 128 x 128 tile: one operand with C % 32 == 0, enough tiles (round 4)
+    switch (p.BN) {
+      case 128: return p.bn_partial == nullptr ? launch_conv_x3<64, 128, 32, 64>(p, s) : launch_conv_x3<128, 64, 64, 32>(p, s);   // (statistics rows are per 128-row tile)
+      case 64: return (small_m || (p.bn_partial == nullptr && blocks128 <= 416)) ? launch_conv_x3<64, 64, 32, 32>(p, s) : launch_conv_x3<128, 64, 64, 32>(p, s);
+      default: return launch_conv_x3<128, 32, 32, 32>(p, s);
+    }
+  }
+  switch (p.BN) {
+    case 128: return small_m ? launch_conv_u32<64, 128, 32, 64>(p, s) : launch_conv<128, 128, 64, 64>(p, s);
+    case 64: return small_m ? launch_conv_u32<64, 64, 32, 32>(p, s) : launch_conv<128, 64, 64, 32>(p, s);
+    default: return launch_conv<128, 32, 32, 32>(p, s);
+  }
 }
 
 static int run_conv(const dn_conv_desc* d, int expect_kind, dn_stream_t stream) {
@@ -2291,27 +2283,7 @@ static int run_conv(const dn_conv_desc* d, int expect_kind, dn_stream_t stream) 
   if (lds3_conv_eligible(d, p)) return launch_lds3_conv(d, p, s);
   if (lds3k_conv_eligible(d, p)) return launch_lds3k_conv(d, p, s);
   if (thin_conv_eligible(d, p)) return launch_thin_conv(p, s);
-  // Few row tiles (the 4x13 / 8x26 decoder levels at b32: 13-52 tiles of 128 rows) leave most of the 256 CUs without a block;
-  // 64-row tiles double the block count at the same per-wave MFMA density along N.  Not with batch statistics: the
-  // bn_partial layout is per 128-row tile.
-  const long long blocks128 = (long long)((p.M + 127) / 128) * (p.Npad / p.BN) * p.nphases;
-  const bool small_m = p.uni32 && p.bn_partial == nullptr && blocks128 <= 208 && !false;
-  if (p.compute == DN_COMPUTE_F32X3 && p.uni32 && !false && !knobs().no_x3_direct && (p.BN >= 64 || false)) {
-    // (the 32-wide N tile -- one 32 x 32 tile per wave, 12 matrix instructions per chunk against five split-and-store items -- measured
-    //  4-17 % slower than the fp32 instruction: it stays on that)
-    // fp32 products on the bf16 matrix cores (wave tiles of at most 2 x 32 x 32: the 128-wide N tile runs as 64-row blocks)
-    if (conv_x3b_eligible(p)) return launch_conv_x3b(p, s);       // 128 x 128 tile: one operand with C % 32 == 0, enough tiles (round 4)
-    switch (p.BN) {
-      case 128: return p.bn_partial == nullptr ? launch_conv_x3<64, 128, 32, 64>(p, s) : launch_conv_x3<128, 64, 64, 32>(p, s);   // (statistics rows are per 128-row tile)
-      case 64: return (small_m || (p.bn_partial == nullptr && blocks128 <= 416)) ? launch_conv_x3<64, 64, 32, 32>(p, s) : launch_conv_x3<128, 64, 64, 32>(p, s);
-      default: return launch_conv_x3<128, 32, 32, 32>(p, s);
-    }
-  }
-  switch (p.BN) {
-    case 128: return small_m ? launch_conv_u32<64, 128, 32, 64>(p, s) : launch_conv<128, 128, 64, 64>(p, s);
-    case 64: return small_m ? launch_conv_u32<64, 64, 32, 32>(p, s) : launch_conv<128, 64, 64, 32>(p, s);
-    default: return launch_conv<128, 32, 32, 32>(p, s);
-  }
+  return launch_tiled_conv(p, s);
 }
 
 template <int BNW, int WNn, int WKk, bool ALLVEC>
@@ -2341,7 +2313,7 @@ static int launch_wgrad_u32(const IgemmParams& p, hipStream_t stream) {
 
 template <int BNW, int WNn, int WKk>
 static int launch_wgrad(const IgemmParams& p, hipStream_t stream) {
-  if (p.wg_uniform && !false)
+  if (p.wg_uniform)
     return p.any_affine ? launch_wgrad_u32<BNW, WNn, WKk, true>(p, stream) : launch_wgrad_u32<BNW, WNn, WKk, false>(p, stream);
   return p.allvec ? launch_wgrad_v<BNW, WNn, WKk, true>(p, stream) : launch_wgrad_v<BNW, WNn, WKk, false>(p, stream);
 }
@@ -2375,6 +2347,11 @@ static void choose_splits(IgemmParams* p) {
   p->splits = (p->M + per - 1) / per;
 }
 
+// workspace of the tiled weight-gradient kernels: one [Npad][Kp] slab per split (after choose_splits)
+static size_t generic_wgrad_workspace_bytes(const IgemmParams& p) {
+  return (size_t)p.splits * p.Npad * p.ph[0].nchunks * kChunk * sizeof(float);
+}
+
 int launch_wgrad_reduce(const IgemmParams& p, float* dw, hipStream_t stream) {
   const long long total = (long long)p.Ntot * p.ph[0].nchunks * kChunk;
   int blocks = (int)((total + 63) / 64);
@@ -2393,7 +2370,7 @@ static int generic_wgrad(const dn_conv_desc* fwd, IgemmParams& p, const float* d
                          hipStream_t s) {
   int rc = DN_OK;
   choose_splits(&p);
-  const size_t need = (size_t)p.splits * p.Npad * p.ph[0].nchunks * kChunk * sizeof(float);
+  const size_t need = generic_wgrad_workspace_bytes(p);
   DN_REQUIRE(workspace_bytes >= need, DN_ERR_WORKSPACE, "wgrad workspace too small: %zu < %zu", workspace_bytes, need);
   p.ws = reinterpret_cast<float*>(workspace);
   if (fwd->kind == DN_CONV_FWD) {
@@ -2445,7 +2422,7 @@ static int generic_wgrad(const dn_conv_desc* fwd, IgemmParams& p, const float* d
 // the one trailing channel (9 columns of dw).  iconv2 at 32 images: 0.272 -> 0.15 ms; config 4's 321 -> 64 @120x160: 1.25 -> 0.5 ms.
 static bool wgrad_split_plans(const dn_conv_desc* fwd, dn_conv_desc* d1, dn_conv_desc* d2, IgemmParams* p1, IgemmParams* p2, size_t* w1,
                               size_t* w2) {
-  if (false || fwd->kind != DN_CONV_FWD || fwd->n_in < 2 || fwd->in[fwd->n_in - 1].C != 1) return false;
+  if (fwd->kind != DN_CONV_FWD || fwd->n_in < 2 || fwd->in[fwd->n_in - 1].C != 1) return false;
   *d1 = *fwd;
   d1->n_in = fwd->n_in - 1;
   *d2 = *fwd;
@@ -2465,7 +2442,7 @@ static bool wgrad_split_plans(const dn_conv_desc* fwd, dn_conv_desc* d1, dn_conv
   p2->in[0].ch_off = cin_total - 1;              // (packed_to_framework: the column block of this channel in the full weight tensor)
   p2->D1 = cin_total;
   choose_splits(p2);
-  *w2 = (size_t)p2->splits * p2->Npad * p2->ph[0].nchunks * kChunk * sizeof(float);
+  *w2 = generic_wgrad_workspace_bytes(*p2);
   return true;
 }
 
@@ -2504,6 +2481,33 @@ static void tap_window_plan(const IgemmParams& full, int w, int nw, IgemmParams*
   }
 }
 
+// The weight-gradient kernel families in front of the tiled kernel, in priority order.  dn_conv_wgrad_workspace_bytes takes the
+// largest workspace_bytes of the eligible rows; dn_conv2d_wgrad launches the first eligible row whose workspace fits (a caller
+// that brought less falls through to the next row, in the end to the tiled kernel).  A new family adds one row here.
+struct WgradFamily {
+  const char* name;
+  bool (*eligible)(const dn_conv_desc* fwd, const IgemmParams& p);
+  size_t (*workspace_bytes)(const dn_conv_desc* fwd, const IgemmParams& p);
+  bool dy_aligned16;            // the kernel reads dy as float4
+  bool (*switched_off)();       // launch-time switch (the sizing ignores it), or nullptr
+  int (*launch)(const dn_conv_desc* fwd, IgemmParams& p, float* dw, hipStream_t s);
+};
+static const WgradFamily kWgradFamilies[] = {
+    {"head", head_wgrad_eligible, [](const dn_conv_desc*, const IgemmParams& p) { return head_wgrad_workspace_bytes(p); }, false,
+     [] { return knobs().no_direct; },       // (the head has one operand; its slabs are an argument of their own)
+     [](const dn_conv_desc*, IgemmParams& p, float* dw, hipStream_t s) { return launch_head_wgrad(p, dw, p.ws, s); }},
+    {"winograd", wino_wgrad_eligible, [](const dn_conv_desc*, const IgemmParams& p) { return wino_wgrad_workspace_bytes(p); }, false, nullptr,
+     [](const dn_conv_desc*, IgemmParams& p, float* dw, hipStream_t s) { return launch_wino_wgrad(p, dw, s); }},
+    {"lds3", lds3_wgrad_eligible, [](const dn_conv_desc*, const IgemmParams& p) { return lds3_wgrad_workspace_bytes(p); }, true, nullptr,
+     launch_lds3_wgrad},
+    {"lds3k", lds3k_wgrad_eligible, [](const dn_conv_desc*, const IgemmParams& p) { return lds3k_wgrad_workspace_bytes(p); }, true, nullptr,
+     launch_lds3k_wgrad},
+    // 7x7 / stride-2 first layers on NCHW images (dn_stemk.hip)
+    {"stemk", stemk_wgrad_eligible, stemk_wgrad_workspace_bytes, true, nullptr, launch_stemk_wgrad},
+    {"thin", thin_wgrad_eligible, [](const dn_conv_desc*, const IgemmParams& p) { return thin_wgrad_workspace_bytes(p); }, false, nullptr,
+     [](const dn_conv_desc*, IgemmParams& p, float* dw, hipStream_t s) { return launch_thin_wgrad(p, dw, s); }},
+};
+
 extern "C" {
 
 int64_t dn_pack_entry_bytes(void) { return (int64_t)sizeof(PackEntry); }
@@ -2521,8 +2525,7 @@ int dn_pack_entry_fill(const dn_conv_desc* d, const float* w, float* w_packed, v
     e->NS = ((e->p.Ntot + 63) / 64 * 64) / 32;
   } else {
     e->wino = 0;
-    const KPhase& last = e->p.ph[e->p.nphases - 1];
-    e->total = last.w_off + (long long)e->p.Npad * last.nchunks * kChunk;
+    e->total = direct_packed_elems(e->p);
     e->NS = 0;
   }
   return e->wino;
@@ -2556,8 +2559,7 @@ int dn_conv_pack_weights(const dn_conv_desc* d, const float* w, float* w_packed,
   DN_REQUIRE(w != nullptr && w_packed != nullptr, DN_ERR_BAD_ARG, "null weight pointer");
   if (const int wl = wino_layout(d, p))
     return wl == 1 ? launch_wino_pack(p, w, w_packed, as_stream(stream)) : launch_wino_pack16(p, w, w_packed, wl == 3 ? 3 : 1, as_stream(stream));
-  const KPhase& last = p.ph[p.nphases - 1];
-  const long long total = last.w_off + (long long)p.Npad * last.nchunks * kChunk;
+  const long long total = direct_packed_elems(p);
   if (total == 0) return DN_OK;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
@@ -2574,13 +2576,9 @@ size_t dn_conv_wgrad_workspace_bytes(const dn_conv_desc* fwd) {
   IgemmParams p;
   if (build_plan(fwd, true, &p) != DN_OK) return 0;
   choose_splits(&p);
-  size_t need = (size_t)p.splits * p.Npad * p.ph[0].nchunks * kChunk * sizeof(float);
-  if (head_wgrad_eligible(fwd, p) && head_wgrad_workspace_bytes(p) > need) need = head_wgrad_workspace_bytes(p);
-  if (wino_wgrad_eligible(fwd, p) && wino_wgrad_workspace_bytes(p) > need) need = wino_wgrad_workspace_bytes(p);
-  if (thin_wgrad_eligible(fwd, p) && thin_wgrad_workspace_bytes(p) > need) need = thin_wgrad_workspace_bytes(p);
-  if (lds3_wgrad_eligible(fwd, p) && lds3_wgrad_workspace_bytes(p) > need) need = lds3_wgrad_workspace_bytes(p);
-  if (lds3k_wgrad_eligible(fwd, p) && lds3k_wgrad_workspace_bytes(p) > need) need = lds3k_wgrad_workspace_bytes(p);
-  if (stemk_wgrad_workspace_bytes(fwd, p) > need) need = stemk_wgrad_workspace_bytes(fwd, p);
+  size_t need = generic_wgrad_workspace_bytes(p);
+  for (const WgradFamily& f : kWgradFamilies)
+    if (f.eligible(fwd, p) && f.workspace_bytes(fwd, p) > need) need = f.workspace_bytes(fwd, p);
   {
     dn_conv_desc d1, d2;
     IgemmParams p1, p2;
@@ -2592,8 +2590,7 @@ size_t dn_conv_wgrad_workspace_bytes(const dn_conv_desc* fwd) {
     IgemmParams q;
     tap_window_plan(p, w, nw, &q);
     choose_splits(&q);
-    const size_t wneed = (size_t)q.splits * q.Npad * q.ph[0].nchunks * kChunk * sizeof(float);
-    if (wneed > need) need = wneed;
+    if (generic_wgrad_workspace_bytes(q) > need) need = generic_wgrad_workspace_bytes(q);
   }
   return need;
 }
@@ -2604,40 +2601,14 @@ int dn_conv2d_wgrad(const dn_conv_desc* fwd, const float* dy, float* dw, void* w
   int rc = build_plan(fwd, true, &p);
   if (rc != DN_OK) return rc;
   DN_REQUIRE(dy != nullptr && dw != nullptr && workspace != nullptr, DN_ERR_BAD_ARG, "null pointer");
-  if (head_wgrad_eligible(fwd, p) && workspace_bytes >= head_wgrad_workspace_bytes(p) && !knobs().no_direct) {
-    DN_REQUIRE(p.in[0].p != nullptr, DN_ERR_BAD_ARG, "operand 0 has no data");
-    p.g = dy;
-    return launch_head_wgrad(p, dw, reinterpret_cast<float*>(workspace), as_stream(stream));
-  }
-  if (wino_wgrad_eligible(fwd, p) && workspace_bytes >= wino_wgrad_workspace_bytes(p)) {
+  const hipStream_t s = as_stream(stream);
+  for (const WgradFamily& f : kWgradFamilies) {
+    if (!f.eligible(fwd, p) || (f.switched_off && f.switched_off()) || workspace_bytes < f.workspace_bytes(fwd, p)) continue;
+    if (f.dy_aligned16 && (reinterpret_cast<uintptr_t>(dy) & 15) != 0) continue;
     for (int i = 0; i < p.n_in; ++i) DN_REQUIRE(p.in[i].p != nullptr, DN_ERR_BAD_ARG, "operand %d has no data", i);
     p.g = dy;
     p.ws = reinterpret_cast<float*>(workspace);
-    return launch_wino_wgrad(p, dw, as_stream(stream));
-  }
-  if (lds3_wgrad_eligible(fwd, p) && workspace_bytes >= lds3_wgrad_workspace_bytes(p) && (reinterpret_cast<uintptr_t>(dy) & 15) == 0) {
-    for (int i = 0; i < p.n_in; ++i) DN_REQUIRE(p.in[i].p != nullptr, DN_ERR_BAD_ARG, "operand %d has no data", i);
-    p.g = dy;
-    p.ws = reinterpret_cast<float*>(workspace);
-    return launch_lds3_wgrad(fwd, p, dw, as_stream(stream));
-  }
-  if (lds3k_wgrad_eligible(fwd, p) && workspace_bytes >= lds3k_wgrad_workspace_bytes(p) && (reinterpret_cast<uintptr_t>(dy) & 15) == 0) {
-    for (int i = 0; i < p.n_in; ++i) DN_REQUIRE(p.in[i].p != nullptr, DN_ERR_BAD_ARG, "operand %d has no data", i);
-    p.g = dy;
-    p.ws = reinterpret_cast<float*>(workspace);
-    return launch_lds3k_wgrad(fwd, p, dw, as_stream(stream));
-  }
-  if (stemk_wgrad_eligible(fwd, p) && workspace_bytes >= stemk_wgrad_workspace_bytes(fwd, p) && (reinterpret_cast<uintptr_t>(dy) & 15) == 0) {
-    for (int i = 0; i < p.n_in; ++i) DN_REQUIRE(p.in[i].p != nullptr, DN_ERR_BAD_ARG, "operand %d has no data", i);
-    p.g = dy;
-    p.ws = reinterpret_cast<float*>(workspace);
-    return launch_stemk_wgrad(fwd, p, dw, as_stream(stream));        // 7x7 / stride-2 first layers on NCHW images (dn_stemk.hip)
-  }
-  if (thin_wgrad_eligible(fwd, p) && workspace_bytes >= thin_wgrad_workspace_bytes(p)) {
-    for (int i = 0; i < p.n_in; ++i) DN_REQUIRE(p.in[i].p != nullptr, DN_ERR_BAD_ARG, "operand %d has no data", i);
-    p.g = dy;
-    p.ws = reinterpret_cast<float*>(workspace);
-    return launch_thin_wgrad(p, dw, as_stream(stream));
+    return f.launch(fwd, p, dw, s);
   }
   {
     dn_conv_desc d1, d2;
@@ -2648,24 +2619,24 @@ int dn_conv2d_wgrad(const dn_conv_desc* fwd, const float* dy, float* dw, void* w
       if (wino_wgrad_eligible(&d1, p1)) {
         p1.g = dy;
         p1.ws = reinterpret_cast<float*>(workspace);
-        rc = launch_wino_wgrad(p1, dw, as_stream(stream));
+        rc = launch_wino_wgrad(p1, dw, s);
       } else {
-        rc = generic_wgrad(&d1, p1, dy, dw, workspace, w1, as_stream(stream));
+        rc = generic_wgrad(&d1, p1, dy, dw, workspace, w1, s);
       }
       if (rc != DN_OK) return rc;
-      return generic_wgrad(&d2, p2, dy, dw, reinterpret_cast<char*>(workspace) + w1, w2, as_stream(stream));
+      return generic_wgrad(&d2, p2, dy, dw, reinterpret_cast<char*>(workspace) + w1, w2, s);
     }
   }
   if (const int nw = tap_windows(p); nw > 1 && fwd->kind == DN_CONV_FWD) {
     for (int w = 0; w < nw; ++w) {
       IgemmParams q;
       tap_window_plan(p, w, nw, &q);
-      rc = generic_wgrad(fwd, q, dy, dw, workspace, workspace_bytes, as_stream(stream));
+      rc = generic_wgrad(fwd, q, dy, dw, workspace, workspace_bytes, s);
       if (rc != DN_OK) return rc;
     }
     return DN_OK;
   }
-  return generic_wgrad(fwd, p, dy, dw, workspace, workspace_bytes, as_stream(stream));
+  return generic_wgrad(fwd, p, dy, dw, workspace, workspace_bytes, s);
 }
 
 }  // extern "C"

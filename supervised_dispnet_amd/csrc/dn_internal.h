@@ -204,6 +204,12 @@ static inline unsigned fastdiv_magic(unsigned d) { return d <= 1 ? 0xFFFFFFFFu :
 
 int build_plan(const dn_conv_desc* d, bool for_wgrad, IgemmParams* p);
 
+// elements of the direct (implicit-GEMM) packed weight layout: [phase][Npad][nchunks * kChunk], phases back to back
+inline long long direct_packed_elems(const IgemmParams& p) {
+  const KPhase& last = p.ph[p.nphases - 1];
+  return last.w_off + (long long)p.Npad * last.nchunks * kChunk;
+}
+
 // one row of the batched weight re-lay table (dn_pack_entry_fill / dn_pack_many): everything a pack kernel takes as arguments
 struct PackEntry {
   IgemmParams p;
@@ -230,7 +236,10 @@ __device__ __forceinline__ unsigned fastdiv_dev(unsigned n, unsigned d, unsigned
   return q;
 }
 
-// dn_direct.hip: matrix-core-free kernels for the one-channel disparity heads, dispatched from the conv entry points
+// ---- kernel families.  Which one a conv call runs is decided in dn_conv.hip and nowhere else: forward / input gradient by the chain of
+// *_eligible calls in run_conv (ending in launch_tiled_conv), the weight gradient by the rows of kWgradFamilies (sizing and launch
+// read the same rows), then the leading-pieces split, the tap windows and the tiled kernel.
+// dn_direct.hip: matrix-core-free kernels for the one-channel disparity heads
 bool head_fwd_eligible(const dn_conv_desc* d, const IgemmParams& p);
 int launch_head_fwd(const IgemmParams& p, hipStream_t stream);
 bool head_fwd_fuses_reciprocal(const dn_conv_desc* d, const IgemmParams& p);
@@ -248,7 +257,7 @@ int launch_wino_conv(IgemmParams& p, hipStream_t stream);
 bool wino_folds_bn_finalize(const IgemmParams& p);   // the launch will finish the BatchNorm statistics / the BatchNorm-backward sums itself
 bool wino_folds_bn_sums(const IgemmParams& p);
 int wino_splitk_choice(const IgemmParams& p);
-size_t conv_x3_splitk_workspace_upper_bytes(const IgemmParams& p);   // dn_conv.hip: K split of the three-piece direct kernel
+size_t conv_x3_splitk_workspace_upper_bytes(const IgemmParams& p);   // dn_conv.hip: K split of the three-piece direct kernel, over the tile shapes launch_tiled_conv may pick
 size_t wino_splitk_workspace_bytes(const IgemmParams& p);
 // dn_winograd_wgrad.hip: Winograd weight gradient of the same layers (operands and output channels multiples of 64)
 bool wino_wgrad_eligible(const dn_conv_desc* fwd, const IgemmParams& p);

@@ -417,8 +417,7 @@ int64_t dn_conv_packed_weight_elems(const dn_conv_desc* d) {
   dn::IgemmParams p;
   if (dn::build_plan(d, false, &p) != DN_OK) return -1;
   if (const int wl = dn::wino_layout(d, p)) return dn::wino_packed_floats(p, wl);
-  const dn::KPhase& last = p.ph[p.nphases - 1];
-  return last.w_off + (int64_t)p.Npad * last.nchunks * dn::kChunk;
+  return dn::direct_packed_elems(p);
 }
 
 int32_t dn_conv_weight_layout(const dn_conv_desc* d) {
@@ -442,7 +441,7 @@ int32_t dn_conv_fwd_fuses_reciprocal(const dn_conv_desc* d) {
 int32_t dn_conv_dgrad_fuses_bn_sums(const dn_conv_desc* d) {
   dn::IgemmParams p;
   if (d == nullptr || dn::build_plan(d, false, &p) != DN_OK) return -1;
-  if (d->kind != DN_CONV_DGRAD || false) return 0;
+  if (d->kind != DN_CONV_DGRAD) return 0;
   if (dn::wino_layout(d, p) == 0) return 0;
   const dn_result& r = d->out[0];
   const bool dense = d->n_out == 1 && !r.accumulate && (r.C & 3) == 0 && r.stride_w == r.C && r.stride_h == (int64_t)d->OW * r.C &&
@@ -469,9 +468,9 @@ int32_t dn_conv_dgrad_folds_bn_sums(const dn_conv_desc* d) {
 int64_t dn_conv_splitk_workspace_bytes(const dn_conv_desc* d) {
   dn::IgemmParams p;
   if (d == nullptr || dn::build_plan(d, false, &p) != DN_OK) return -1;
-  if (dn::wino_layout(d, p) == 3) return (int64_t)dn::wino_splitk_workspace_bytes(p);
-  if (dn::wino_layout(d, p) != 0) return 0;
-  return (int64_t)dn::conv_x3_splitk_workspace_upper_bytes(p);
+  const int wl = dn::wino_layout(d, p);
+  if (wl == 3) return (int64_t)dn::wino_splitk_workspace_bytes(p);
+  return wl != 0 ? 0 : (int64_t)dn::conv_x3_splitk_workspace_upper_bytes(p);
 }
 
 // Test/diagnostic hook (host only, no device work): dump the plan as int32s.

@@ -1099,7 +1099,7 @@ int dn_bn_bwd_apply_relu(float* da_dy, const float* y, const float* scale, const
   hipStream_t s = as_stream(stream);
   int rc = bn_bwd_sums_to_params(partial, partial_rows, partial_stride, partial_offset, C, dgamma, dbeta, s, "dn_bn_bwd_apply_relu");
   if (rc != DN_OK) return rc;
-  const bool hoisted = C % 4 == 0 && kThreads % (C / 4) == 0 && !false;
+  const bool hoisted = C % 4 == 0 && kThreads % (C / 4) == 0;
   set_last_kernel(hoisted ? "dn::bn_bwd_apply_relu_hoisted_kernel" : "dn::bn_bwd_apply_relu_kernel");
   if (hoisted)
     DN_LAUNCH(bn_bwd_apply_relu_hoisted_kernel, dim3(ew_blocks((rows * (C / 4) + 3) / 4)), dim3(kThreads), 0, s, da_dy, y, scale, shift, mean,
