@@ -592,6 +592,29 @@ int dn_nyu_val_resize(const float* src, int32_t B, int32_t IH, int32_t IW, int32
                       float* dst, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Evaluation chain on the device (reference test_disp.py:391-398, :453-469).  pred = the network-resolution depth [B,h,w] fp32.
+ * dn_eval_normalize: dst = ((div255 ? x / 255 : x) - mean[c]) / std[c] over fp32 frames [B,3,HW] (IEEE fp32, that order; mean_host /
+ * std_host: 3 floats each on the host) -- the frames test_disp.py does not resize, and NYU's, which it does not divide by 255.
+ * dn_zoom3_prefilter writes coef = double[B][h][w], the cubic B-spline coefficients (mirror boundaries, fp64; 3 <= h, 3 <= w <= 2048).
+ * dn_zoom3_clip is scipy.ndimage.zoom(pred[b], (H_b/h, W_b/w)) with scipy's defaults (order 3, mode 'constant', cval 0,
+ * grid_mode=False) followed by .clip(lo, hi): out_hw = int32[B][2] {H_b, W_b} and out_off = int64[B] (element offsets) on the device;
+ * image b is written as H_b x W_b fp32 at out + out_off[b].  max_h / max_w: the largest H_b / W_b of the batch (sizes the grid).
+ * Per axis, output o reads x = o * ((n-1)/(O-1)) (fp64; 0 if O == 1); x outside [0, n-1] gives exactly 0 (then lo).
+ * dn_eval_errors: per image over the pixels with mask != 0 of the same ragged layout (npix[b] elements at off[b]):
+ * scale_mode 0: 1; 1: fixed_scale; 2: np.median(gt) / np.median(pred) (fp32, even counts average the two middle elements);
+ * pred * scale is rounded to fp32; a1..a3 compare max(gt/pred, pred/gt) in IEEE fp32; the four means take fp64 terms and fp64 sums.
+ * out = float[B][8]: abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, scale (NaN for an empty mask).  One block per image does the
+ * selection and the sums, so there is no workspace.  Masked gt and pred must be positive (the selection orders bit patterns).
+ * ------------------------------------------------------------------------------------------------------------ */
+int dn_eval_normalize(const float* src, int32_t B, int64_t HW, int32_t div255, const float* mean_host, const float* std_host, float* dst,
+                      dn_stream_t stream);
+int dn_zoom3_prefilter(const float* pred, int32_t B, int32_t h, int32_t w, double* coef, dn_stream_t stream);
+int dn_zoom3_clip(const double* coef, int32_t B, int32_t h, int32_t w, const int32_t* out_hw, const int64_t* out_off, int32_t max_h,
+                  int32_t max_w, float lo, float hi, float* out, dn_stream_t stream);
+int dn_eval_errors(const float* gt, const float* pred, const uint8_t* mask, const int64_t* off, const int32_t* npix, int32_t B,
+                   int32_t scale_mode, float fixed_scale, float* out, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Attainable-peak probes (SURVEY.md section 8d "Peaks"; used by bench.py only): a float4 streaming copy of n floats
  * (n % 4 == 0, 16-byte aligned; moves 8*n bytes) and a register-resident v_mfma_f32_32x32x2_f32 loop
  * (out: blocks*256 floats; dn_ubench_mfma_f32_flops = the FLOPs one launch executes).

@@ -184,6 +184,10 @@ SIGNATURES = {
     "dn_nyu_prefilter": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_nyu_train_resample": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dn_nyu_val_resize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "dn_eval_normalize": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "dn_zoom3_prefilter": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "dn_zoom3_clip": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _f, _f, _vp, _vp]),
+    "dn_eval_errors": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f, _vp, _vp]),
     "dn_ubench_copy": (C.c_int, [_vp, _vp, _i64, _vp]),
     "dn_ubench_mfma_f32_flops": (_i64, [_i32, _i32]),
     "dn_ubench_mfma_f32": (C.c_int, [_vp, _i32, _i32, _vp]),

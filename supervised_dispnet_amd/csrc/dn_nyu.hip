@@ -17,24 +17,18 @@
 // convex combination of values inside [min, max] leaves it only by fp64 rounding, far below the fp32 cast that follows.
 // Per-sample parameters come as double[B][8] = {flip, angle (degrees), crop row, crop column, s, gain, 0, 0}; the host draws them.
 #include "dn_internal.h"
+#include "dn_spline.h"
 
 #pragma clang fp contract(off)
 
 namespace dn {
 
 constexpr int kNyuThreads = 256;
-constexpr double kPole = -0x1.126145e9ecd58p-2;    // sqrt(3) - 2 in fp64
-constexpr double kGain = 0x1.7fffffffffffep+2;     // (1 - z) * (1 - 1/z) as scipy evaluates it (one line's gain)
 constexpr int kTileH = 16, kTileW = 64;            // output tile of the train resample
 constexpr int kRegH = kTileH + 1, kRegW = kTileW + 1;   // crop-space window a tile reads at s >= 1
 constexpr int kRowLines = 8;                       // lines per block of the axis-1 prefilter pass
 constexpr int kRowThreads = 64;
 constexpr int kMaxRowW = 1024;
-
-static __device__ __forceinline__ int mirror_idx(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i > n - 1 ? 2 * (n - 1) - i : i;
-}
 
 // ---- per-sample min / max over all five stored channels: partial[b][chunk] = (min, max)
 __global__ void __launch_bounds__(kNyuThreads) nyu_minmax_kernel(const float* __restrict__ raw, long long per_sample, float* __restrict__ partial) {
@@ -75,44 +69,7 @@ __global__ void __launch_bounds__(kNyuThreads) nyu_prefilter_cols_kernel(const f
   const int sj = params[b * 8 + 0] != 0.0 ? W - 1 - j : j;
   const float* src = raw + ((long long)b * 5 + ch) * H * W + sj;
   double* dst = coef + ((long long)b * 4 + ch) * H * W + j;
-  const double z = kPole;
-  // causal init over the mirrored line (needs every element: read them from the source, gain applied on the fly)
-  const double z_n_1 = pow(z, (double)(H - 1));
-  double c0 = (double)src[0] * kGain + z_n_1 * ((double)src[(long long)(H - 1) * W] * kGain);
-  double z_i = z;
-#pragma unroll 8
-  for (int i = 1; i < H - 1; ++i) {
-    c0 += z_i * ((double)src[(long long)i * W] * kGain + z_n_1 * ((double)src[(long long)(H - 1 - i) * W] * kGain));
-    z_i *= z;
-  }
-  double prev = c0 / (1.0 - z_n_1 * z_n_1);
-  dst[0] = prev;
-  double before_last = prev;
-#pragma unroll 8
-  for (int i = 1; i < H; ++i) {
-    const double v = (double)src[(long long)i * W] * kGain + z * prev;
-    if (i == H - 2) before_last = v;
-    dst[(long long)i * W] = v;
-    prev = v;
-  }
-  double next = (z * before_last + prev) * z / (z * z - 1.0);
-  dst[(long long)(H - 1) * W] = next;
-  // anti-causal pass: the causal values of 8 rows are loaded before the dependent chain walks them
-  int i = H - 2;
-  for (; i >= 7; i -= 8) {
-    double d[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) d[k] = dst[(long long)(i - k) * W];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      next = z * (next - d[k]);
-      dst[(long long)(i - k) * W] = next;
-    }
-  }
-  for (; i >= 0; --i) {
-    next = z * (next - dst[(long long)i * W]);
-    dst[(long long)i * W] = next;
-  }
+  spline_prefilter_column(src, dst, H, W);
 }
 
 // ---- prefilter along axis 1: kRowLines lines of W doubles staged in LDS (coalesced in and out), one thread per line filters.
@@ -124,46 +81,10 @@ __global__ void __launch_bounds__(kRowThreads) nyu_prefilter_rows_kernel(long lo
   for (int e = threadIdx.x; e < nl * W; e += kRowThreads) sline[e] = g[e];
   __syncthreads();
   if ((int)threadIdx.x < nl) {
-    // the same recurrences as the column pass; the gain is applied where a value is first read, the running value stays in a register
-    double* c = sline + threadIdx.x * W;
-    const int n = W;
-    const double z = kPole;
-    const double z_n_1 = pow(z, (double)(n - 1));
-    double c0 = c[0] * kGain + z_n_1 * (c[n - 1] * kGain);
-    double z_i = z;
-#pragma unroll 8
-    for (int i = 1; i < n - 1; ++i) {
-      c0 += z_i * (c[i] * kGain + z_n_1 * (c[n - 1 - i] * kGain));
-      z_i *= z;
-    }
-    double p = c0 / (1.0 - z_n_1 * z_n_1);
-    c[0] = p;
-    double before_last = p;
-#pragma unroll 8
-    for (int i = 1; i < n; ++i) {
-      p = c[i] * kGain + z * p;
-      if (i == n - 2) before_last = p;
-      c[i] = p;
-    }
-    p = (z * before_last + p) * z / (z * z - 1.0);
-    c[n - 1] = p;
-#pragma unroll 8
-    for (int i = n - 2; i >= 0; --i) {
-      p = z * (p - c[i]);
-      c[i] = p;
-    }
+    spline_prefilter_line(sline + threadIdx.x * W, W);
   }
   __syncthreads();
   for (int e = threadIdx.x; e < nl * W; e += kRowThreads) g[e] = sline[e];
-}
-
-// cubic B-spline weights of the four taps floor(x)-1 .. floor(x)+2 at fraction t (scipy's form, last weight = 1 - the others)
-static __device__ __forceinline__ void cubic_weights(double t, double* w) {
-  const double z = 1.0 - t;
-  w[0] = z * z * z / 6.0;
-  w[1] = (t * t * (t - 2.0) * 3.0 + 4.0) / 6.0;
-  w[2] = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0;
-  w[3] = 1.0 - w[0] - w[1] - w[2];
 }
 
 // scipy.ndimage.rotate's order-3 value at source (y, x) of one H x W coefficient plane: 0 outside [0, H-1] x [0, W-1], mirrored taps

@@ -1,0 +1,187 @@
+"""Batched evaluation of test_disp.py's chain on the device (eval_disp.py --eval-batch): everything between the
+resized input frames and the seven error numbers of an image stays on the GPU.
+
+Per batch the host does what test_disp.evaluate_sample does before the forward (scipy.misc.imresize semantics, transpose) and packs
+ground truth and masks; the device normalises, runs ONE eval-mode forward at batch B, takes 1/disp (or the SID decode), and then
+dn_zoom3_prefilter -> dn_zoom3_clip -> dn_eval_errors.  Ground truths of a batch may differ in size (KITTI: 370x1226, 374x1238,
+375x1242, 376x1241), so the zoomed predictions, the ground truth and the masks share one ragged layout: image b is H_b x W_b elements
+at element offset off[b], offsets aligned to RAGGED_ALIGN elements.  [B][8] floats come back; the network-resolution depth only when
+the caller keeps predictions.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, kitti_eval as KE
+
+RAGGED_ALIGN = 4          # elements: the mask's 4-byte reads and the fp32 rows' 16 bytes start aligned
+SCALE_NONE, SCALE_FIXED, SCALE_MEDIAN = 0, 1, 2
+STEREO_SCALE = 5.4        # test_disp.py:394
+
+
+def ragged_layout(shapes, align=RAGGED_ALIGN):
+    """[(H_b, W_b)] -> (hw int32 [B, 2], off int64 [B], npix int32 [B], total elements)."""
+    hw = np.asarray(shapes, dtype=np.int32).reshape(-1, 2)
+    npix = (hw[:, 0].astype(np.int64) * hw[:, 1]).astype(np.int32)
+    off = np.zeros(len(hw), dtype=np.int64)
+    pos = 0
+    for b, n in enumerate(npix):
+        off[b] = pos
+        pos += -(-int(n) // align) * align
+    return hw, off, npix, pos
+
+
+def pack_ragged(arrays, dtype, off, total):
+    """2-D arrays -> one flat array of `total` elements of `dtype`, array b raveled at off[b] (gaps are zero)."""
+    flat = np.zeros(total, dtype=dtype)
+    for a, o in zip(arrays, off):
+        flat[o:o + a.size] = np.asarray(a).reshape(-1)
+    return flat
+
+
+def unpack_ragged(flat, hw, off):
+    return [flat[o:o + int(h) * int(w)].reshape(int(h), int(w)) for (h, w), o in zip(hw, off)]
+
+
+def numpy_median_f32(a):
+    """np.median of a float32 array, spelled out (the rule dn_eval_errors implements): the middle element of the sorted values for an
+    odd count, the float32 (a + b) / 2 of the two middle elements for an even one; NaN for none."""
+    s = np.sort(np.asarray(a, dtype=np.float32).reshape(-1))
+    n = s.size
+    if n == 0:
+        return np.float32(np.nan)
+    lo = s[(n - 1) // 2]
+    return lo if n % 2 else np.float32(np.float32(lo + s[n // 2]) / np.float32(2))
+
+
+def median_scale_f32(gt, pred):
+    """The scale of --unsupervised / --mono on float32 arrays: a float32 division of the two medians."""
+    return np.float32(numpy_median_f32(gt) / numpy_median_f32(pred))
+
+
+def scale_mode(args):
+    """test_disp.py:391-396 -> (mode, fixed scale)."""
+    if args.unsupervised or args.mono:
+        return SCALE_MEDIAN, 1.0
+    if args.stereo:
+        return SCALE_FIXED, STEREO_SCALE
+    return SCALE_NONE, 1.0
+
+
+def network_size(args):
+    return (256, 352) if args.gt_type == "NYU" else (args.img_height, args.img_width)   # NYU size hard-coded (test_disp.py:154-155)
+
+
+def prepare_frame(args, sample):
+    """The host half of evaluate_sample before the forward: HWC frame, resized like scipy.misc.imresize unless --no-resize or already
+    at the network's size.  Returns a uint8 [h, w, 3] array (resized) or a float32 one (untouched)."""
+    tgt = sample["tgt"]
+    if args.gt_type == "NYU":
+        tgt = np.transpose(tgt, (1, 2, 0))
+    h, w, _ = tgt.shape
+    img_h, img_w = network_size(args)
+    if (not args.no_resize) and (h != img_h or w != img_w):
+        return np.ascontiguousarray(KE.imresize_bilinear(tgt, (img_h, img_w)))
+    return np.ascontiguousarray(tgt, dtype=np.float32)
+
+
+def sample_ground_truth(args, sample, min_depth, max_depth):
+    gt = sample["gt_depth"]
+    if args.gt_type == "NYU" and gt.ndim == 3:
+        gt = gt[0]
+    mask = sample["mask"] if args.gt_type == "KITTI" else (gt > min_depth) & (gt < max_depth)
+    return gt, mask
+
+
+class DeviceEvaluator(object):
+    """evaluate(samples) -> (errors float32 [7, n], [depth at network resolution] or None per sample).  Workspaces grow to the largest
+    batch seen and are reused."""
+
+    def __init__(self, args, disp_net, device, min_depth, max_depth, keep_depth=None):
+        from .data import normalization
+        self.args, self.net, self.device = args, disp_net, torch.device(device)
+        self.lo, self.hi = float(min_depth), float(max_depth)
+        self.keep_depth = (args.output_dir is not None) if keep_depth is None else keep_depth
+        self.mode, self.fixed = scale_mode(args)
+        self.sid = args.network in ("DORN", "disp_vgg_BN_DORN")
+        mean, std = normalization(args.imagenet_normalization, args.monodepth2)
+        self.mean_h, self.std_h = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+        self.mean_d = torch.tensor(mean, dtype=torch.float32, device=self.device)
+        self.std_d = torch.tensor(std, dtype=torch.float32, device=self.device)
+        self.ws = {}
+        self.scales = None                    # the scale each image of the last batch was given
+
+    def _buf(self, name, numel, dtype):
+        t = self.ws.get(name)
+        if t is None or t.numel() < numel:
+            t = self.ws[name] = torch.empty(int(numel), dtype=dtype, device=self.device)
+        return t[:int(numel)]
+
+    def _upload(self, name, host):
+        t = torch.from_numpy(np.ascontiguousarray(host).reshape(-1))
+        d = self._buf(name, t.numel(), t.dtype)
+        d.copy_(t)
+        return d
+
+    def _normalised(self, frames):
+        """[uint8 or float32 HWC frames of one size] -> normalised fp32 [B, 3, h, w] on the device."""
+        B = len(frames)
+        h, w, _ = frames[0].shape
+        if any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("--eval-batch needs frames of one size per batch; use --eval-batch 1 with --no-resize on mixed sizes")
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        img = self._buf("img", B * 3 * h * w, torch.float32).view(B, 3, h, w)
+        kitti = self.args.gt_type == "KITTI"
+        if kitti and all(f.dtype == np.uint8 for f in frames):
+            d = self._upload("u8", np.stack(frames))
+            _lib.call("dn_u8_normalize_flip", d.data_ptr(), None, B, h, w, 3, self.mean_d.data_ptr(), self.std_d.data_ptr(), self.mean_h,
+                      self.std_h, img.data_ptr(), 3 * h * w, h * w, st)
+        else:                                 # frames the host did not resize, and NYU (not divided by 255 in the reference)
+            chw = np.stack([np.transpose(f.astype(np.float32), (2, 0, 1)) for f in frames])
+            d = self._upload("f32", np.ascontiguousarray(chw))
+            _lib.call("dn_eval_normalize", d.data_ptr(), B, h * w, 1 if kitti else 0, self.mean_h, self.std_h, img.data_ptr(), st)
+        return img
+
+    @torch.no_grad()
+    def predict_depth(self, img):
+        """One eval-mode forward at batch B -> depth [B, h, w] fp32, contiguous."""
+        from . import functional, utils as U
+        if self.sid:
+            pred_d, _ = self.net(img)
+            depth = U.get_depth_sid(pred_d, ordinal_c=self.args.ordinal_c, dataset=self.args.gt_type)
+        else:
+            depth = functional.reciprocal(self.net(img))
+        B = img.shape[0]
+        return depth.reshape(B, depth.shape[-2], depth.shape[-1]).contiguous().float()
+
+    def zoom_clip(self, depth, hw, off, total):
+        """depth [B, h, w] on the device -> the ragged zoomed, clipped predictions (a view of a reused workspace)."""
+        B, h, w = depth.shape
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        coef = self._buf("coef", B * h * w, torch.float64)
+        d_hw, d_off = self._upload("hw", hw), self._upload("off", off)
+        zoomed = self._buf("zoomed", total, torch.float32)
+        _lib.call("dn_zoom3_prefilter", depth.data_ptr(), B, h, w, coef.data_ptr(), st)
+        _lib.call("dn_zoom3_clip", coef.data_ptr(), B, h, w, d_hw.data_ptr(), d_off.data_ptr(), int(hw[:, 0].max()), int(hw[:, 1].max()),
+                  self.lo, self.hi, zoomed.data_ptr(), st)
+        return zoomed, d_off
+
+    @torch.no_grad()
+    def evaluate(self, samples):
+        B = len(samples)
+        img = self._normalised([prepare_frame(self.args, s) for s in samples])
+        gts, masks = zip(*(sample_ground_truth(self.args, s, self.lo, self.hi) for s in samples))
+        hw, off, npix, total = ragged_layout([g.shape for g in gts])
+        d_gt = self._upload("gt", pack_ragged(gts, np.float32, off, total))
+        d_mask = self._upload("mask", pack_ragged(masks, np.uint8, off, total))
+        d_npix = self._upload("npix", npix)
+        depth = self.predict_depth(img)
+        zoomed, d_off = self.zoom_clip(depth, hw, off, total)
+        out = self._buf("out", B * 8, torch.float32)
+        _lib.call("dn_eval_errors", d_gt.data_ptr(), zoomed.data_ptr(), d_mask.data_ptr(), d_off.data_ptr(), d_npix.data_ptr(), B, self.mode,
+                  self.fixed, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        res = out.view(B, 8).cpu().numpy()
+        self.scales = res[:, 7].copy()
+        pred = list(depth.cpu().numpy()) if self.keep_depth else [None] * B
+        return np.ascontiguousarray(res[:, :7].T), pred
