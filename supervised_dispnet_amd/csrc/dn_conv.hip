@@ -14,50 +14,11 @@
 #include <type_traits>
 #include <utility>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int LDK = 36;  // padded LDS row (floats) of a [rows][32] K-chunk tile
-
-__device__ __forceinline__ float apply_act(float v, int act, float p0, float p1) {
-  switch (act) {
-    case DN_ACT_RELU: return v > 0.f ? v : 0.f;
-    case DN_ACT_LEAKY: return v > 0.f ? v : v * p0;
-    case DN_ACT_ELU: return v > 0.f ? v : (expf(v) - 1.f);
-    case DN_ACT_SIGMOID_AFFINE: return p0 / (1.f + expf(-v)) + p1;
-    default: return v;
-  }
-}
-
-// ReflectionPad2d index map for v in [-(n-1), 2(n-1)]
-__device__ __forceinline__ int reflect_idx(int v, int n) {
-  const int m = n - 1;
-  int a = v < 0 ? -v : v;
-  a = m - a;
-  a = a < 0 ? -a : a;
-  return m - a;
-}
-
-// Which operand piece does K-chunk `kc` of a phase with `ntaps` taps fall in?  Uniform across the block.
-__device__ __forceinline__ int select_operand(const IgemmParams& p, int ntaps, int kc, int* kc_local) {
-  int s = 0;
-#pragma unroll
-  for (int i = 0; i < DN_MAX_OPERANDS - 1; ++i) {
-    if (s == i && i < p.n_in - 1) {
-      int nch = (ntaps * p.in[i].C + kChunk - 1) / kChunk;
-      if (kc >= nch) {
-        kc -= nch;
-        s = i + 1;
-      }
-    }
-  }
-  *kc_local = kc;
-  return s;
-}
 
 // One 4-wide K group of one row of the A operand.
 struct AGroup {
@@ -448,16 +409,6 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_kernel(const IgemmParams p)
   conv_epilogue<BM, BN, WM, WN>(p, acc, rowpix, As, m0, n0);
 }
 
-// compile-time loop: the body is instantiated once per index, so register arrays indexed by it never become dynamic
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // ------------------------------------------------------------------------------------- forward family, uniform fast path
 // uni32 plans (every operand: C % 32 == 0, float4-addressable, no upsample, < 2 GiB; <= 32 taps; zero padding): a K chunk
 // never straddles a tap or an operand, so (operand, tap, channel base) are BLOCK-UNIFORM per chunk and live on the scalar
@@ -825,11 +776,6 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_u32_kernel(const IgemmParam
 // the scheduled loaders do not take (1-channel pieces, the 3-channel image, upsampled maps) keep the fp32 instruction on the same
 // accumulators (both instructions share the 32 x 32 C/D layout).
 constexpr int X3ROW = 192;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 template <int BM, int BN, int WM, int WN>
 __global__ void __launch_bounds__(256, 2) igemm_conv_x3_kernel(const IgemmParams p) {
   constexpr int WAVES_N = BN / WN;
@@ -1261,7 +1207,6 @@ __global__ void __launch_bounds__(256, 2) igemm_conv_x3_kernel(const IgemmParams
         for (int jn = 0; jn < NI; ++jn)
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            typedef int i32x4 __attribute__((ext_vector_type(4)));
             const i32x4 vi = __builtin_amdgcn_raw_buffer_load_b128(rws, (int)(((z * NQ + (i * NI + jn) * 4 + e) * 256 + tid) * 16), 0, 1 /* glc */);
             const f32x4 v = __builtin_bit_cast(f32x4, vi);
 #pragma unroll

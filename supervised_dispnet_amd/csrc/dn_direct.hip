@@ -4,21 +4,9 @@
 // output column is padded to a 32-wide MFMA tile (97 % of the matrix work wasted, 0.3-0.7 ms per launch at 128x416 b32).
 // Here: one thread per (pixel, 4-channel group), NHWC float4 loads, the 9*C weights in LDS, wave shuffles for the reductions.
 // Dispatch happens inside dn_conv2d_fwd / dn_conv2d_dgrad / dn_conv2d_wgrad (same ABI, same packed-weight layout).
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float head_act(float v, int act, float p0, float p1) {
-  switch (act) {
-    case DN_ACT_RELU: return v > 0.f ? v : 0.f;
-    case DN_ACT_LEAKY: return v > 0.f ? v : v * p0;
-    case DN_ACT_ELU: return v > 0.f ? v : (expf(v) - 1.f);
-    case DN_ACT_SIGMOID_AFFINE: return p0 / (1.f + expf(-v)) + p1;
-    default: return v;
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------- forward
 // y[pix] = act(bias + sum_{tap, c} x[pix*s + tap][c] * w[tap][c]);  packed weights row 0 is exactly w[tap][c] (k = tap*C + c).
@@ -51,7 +39,7 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(const IgemmParams p, int 
     for (int d = 1; d < (1 << LG); d <<= 1) acc += __shfl_xor(acc, d);
     if (live && cg == 0) {
       const KResult& R = p.out[0];
-      float v = head_act(acc + (p.bias ? p.bias[0] : 0.f), p.act, p.act_p0, p.act_p1);
+      float v = apply_act(acc + (p.bias ? p.bias[0] : 0.f), p.act, p.act_p0, p.act_p1);
       float* o = R.p + (long long)n * R.sn + (long long)gy * R.sh + (long long)gx * R.sw;
       if (R.accumulate) v += *o;
       *o = v;
@@ -243,7 +231,7 @@ __global__ void __launch_bounds__(256) head_fwd2_kernel(const IgemmParams p, int
       float acc = bias;
 #pragma unroll
       for (int j = 0; j < 9; ++j) acc += t[(j * (TY + 2) + oy + 1 + p.tdy[j]) * LD + ox + 1 + p.tdx[j]];
-      float v = head_act(acc, p.act, p.act_p0, p.act_p1);
+      float v = apply_act(acc, p.act, p.act_p0, p.act_p1);
       float* op = R.p + (long long)n * R.sn + (long long)gy * R.sh + (long long)gx * R.sw;
       if (R.accumulate) v += *op;
       *op = v;

@@ -199,7 +199,7 @@ struct IgemmParams {
   int nmajor;                // Winograd tile order: q -> (mb, nb) = (q % MT, q / MT) instead of (q / NT, q % NT)
 };
 
-// floor(n / d) for 0 <= n < 2^31 with a precomputed magic (see fastdiv_magic); branch-free
+// magic of d for floor(n / d), 0 <= n < 2^31, which fastdiv_dev (dn_device.h) takes on the device
 static inline unsigned fastdiv_magic(unsigned d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(0x100000000ull / d); }
 
 int build_plan(const dn_conv_desc* d, bool for_wgrad, IgemmParams* p);
@@ -224,17 +224,6 @@ int launch_wino_pack16_many(const PackEntry* tab_dev, int first, int n, int piec
 int launch_wino_pack16(const IgemmParams& p, const float* w, float* wp, int pieces, hipStream_t stream);
 long long wino_packed_floats(const IgemmParams& p, int layout);
 int wino_layout(const dn_conv_desc* d, const IgemmParams& p);
-
-// floor(n/d) on the device with the plan's magic (estimate is exact or one low; branch-free fix-up); *rem = n - q*d
-__device__ __forceinline__ unsigned fastdiv_dev(unsigned n, unsigned d, unsigned M, unsigned* rem) {
-  unsigned q = __umulhi(n, M);
-  unsigned r = n - q * d;
-  const bool fix = r >= d;
-  q += fix ? 1u : 0u;
-  r -= fix ? d : 0u;
-  *rem = r;
-  return q;
-}
 
 // ---- kernel families.  Which one a conv call runs is decided in dn_conv.hip and nowhere else: forward / input gradient by the chain of
 // *_eligible calls in run_conv (ending in launch_tiled_conv), the weight gradient by the rows of kWgradFamilies (sizing and launch

@@ -19,67 +19,9 @@
 // The XCD a block runs on gets a contiguous band of tiles, so the halo rows two neighbouring tiles share are fetched by one L2.
 #include <stdlib.h>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float lds3_act(float v, int act, float p0, float p1) {
-  switch (act) {
-    case DN_ACT_RELU: return v > 0.f ? v : 0.f;
-    case DN_ACT_LEAKY: return v > 0.f ? v : v * p0;
-    case DN_ACT_ELU: return v > 0.f ? v : (expf(v) - 1.f);
-    case DN_ACT_SIGMOID_AFFINE: return p0 / (1.f + expf(-v)) + p1;
-    default: return v;
-  }
-}
-
-// four values at once: ONE (wave-uniform) branch on the activation instead of one per element
-__device__ __forceinline__ f32x4 lds3_act4(f32x4 v, int act, float p0, float p1) {
-  f32x4 r = v;
-  switch (act) {
-    case DN_ACT_RELU:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : 0.f;
-      break;
-    case DN_ACT_LEAKY:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : v[e] * p0;
-      break;
-    case DN_ACT_ELU:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : (expf(v[e]) - 1.f);
-      break;
-    case DN_ACT_SIGMOID_AFFINE:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = p0 / (1.f + expf(-v[e])) + p1;
-      break;
-    default: break;
-  }
-  return r;
-}
-
-// x = h + m + l exactly (round to bf16, subtract, round, subtract: the last residual has <= 8 significant bits)
-__device__ __forceinline__ void split3(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-#pragma unroll
-  for (int e = 0; e < 8; e += 2) {
-    const f32x2 x = f32x2{v[e], v[e + 1]};
-    const bf16x2 h2 = __builtin_convertvector(x, bf16x2);
-    const f32x2 r = x - __builtin_convertvector(h2, f32x2);
-    const bf16x2 m2 = __builtin_convertvector(r, bf16x2);
-    const f32x2 q = r - __builtin_convertvector(m2, f32x2);
-    const bf16x2 l2 = __builtin_convertvector(q, bf16x2);
-    h[e] = h2[0]; h[e + 1] = h2[1];
-    m[e] = m2[0]; m[e + 1] = m2[1];
-    l[e] = l2[0]; l[e + 1] = l2[1];
-  }
-}
 
 struct Lds3Geo {
   int tilesX, tilesY, ntiles;      // tiles per image along x / y, total (N * tilesY * tilesX)
@@ -373,9 +315,9 @@ __global__ void __launch_bounds__(256, 2) lds3_conv_kernel(const IgemmParams p, 
           const int gy = gy0 + ty, gx = gx0 + tx16 * 16 + j;
           const int oy = gy * p.osy + ph.ooy, ox = gx * p.osx + ph.oox;
           const bool ok = gy < p.GH && gx < p.GW && oy < p.OH && ox < p.OW && n0 < p.Ntot && !(DBG && geo.dbgmode == 3 && acc[u][0] != 12345.678f);
-          const f32x4 w4 = lds3_act4(acc[u] + f32x4{bias[0], bias[1], bias[2], bias[3]}, p.act, p.act_p0, p.act_p1);
+          const f32x4 w4 = apply_act4(acc[u] + f32x4{bias[0], bias[1], bias[2], bias[3]}, p.act, p.act_p0, p.act_p1);
           const int off = tbase + (ty * p.osy * (int)R0.sh + tx16 * 16 * p.osx * (int)R0.sw) * 4 + lane_out;
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, w4), rout, ok ? off : -1, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w4), rout, ok ? off : -1, 0, 0);
         }
         continue;
       }
@@ -388,7 +330,7 @@ __global__ void __launch_bounds__(256, 2) lds3_conv_kernel(const IgemmParams p, 
         if (gy < p.GH && gx < p.GW && oy < p.OH && ox < p.OW && n0 < p.Ntot && !(DBG && geo.dbgmode == 3 && acc[u][0] != 12345.678f)) {
           float v[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = lds3_act(acc[u][e] + bias[e], p.act, p.act_p0, p.act_p1);
+          for (int e = 0; e < 4; ++e) v[e] = apply_act(acc[u][e] + bias[e], p.act, p.act_p0, p.act_p1);
           if (vec_store) {
             f32x4* o = reinterpret_cast<f32x4*>(R.p + (long long)n * R.sn + (long long)oy * R.sh + (long long)ox * R.sw + cl);
             f32x4 w4 = f32x4{v[0], v[1], v[2], v[3]};
@@ -433,18 +375,6 @@ __global__ void __launch_bounds__(256, 2) lds3_conv_kernel(const IgemmParams p, 
 // 2 rows x 32 columns = 64 pixels; two waves make one 128-pixel row of the BatchNorm partial-statistics table (sum, M2 about the tile
 // mean; dn_bn_finalize): taken in one pass about a pivot (the wave's first pixel), reduced over the 16 pixel lanes with row-rotate DPP
 // adds, the two halves merged through LDS (Chan).  8 x 32 tiles: 6656 of them at 32 x 128 x 416 = 13 per resident block, no tail.
-template <int ROT>
-__device__ __forceinline__ float dpp_row_ror(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + ROT, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_sum(float v) {      // sum over the 16 lanes of a DPP row, in every lane
-  v += dpp_row_ror<8>(v);
-  v += dpp_row_ror<4>(v);
-  v += dpp_row_ror<2>(v);
-  v += dpp_row_ror<1>(v);
-  return v;
-}
-
 constexpr int STEM_TH = 8, STEM_TW = 32, STEM_ROWS = 10, STEM_COLS = 34, STEM_COLSP = 36, STEM_PLANE = STEM_ROWS * STEM_COLSP;
 
 __global__ void __launch_bounds__(256, 2) stem3_conv_kernel(const IgemmParams p, const Lds3Geo geo) {
@@ -575,7 +505,7 @@ __global__ void __launch_bounds__(256, 2) stem3_conv_kernel(const IgemmParams p,
         for (int m = 0; m < 4; ++m) {
           f32x4 w4;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) w4[e] = lds3_act(acc[u][m][e] + bias[m][e], p.act, p.act_p0, p.act_p1);
+          for (int e = 0; e < 4; ++e) w4[e] = apply_act(acc[u][m][e] + bias[m][e], p.act, p.act_p0, p.act_p1);
           *reinterpret_cast<f32x4*>(o + 16 * m) = w4;
         }
       }

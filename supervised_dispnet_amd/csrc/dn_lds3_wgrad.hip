@@ -15,30 +15,9 @@
 // those fragments are gathered from small fp32 planes (8 ds_read_b32) and split in registers.
 #include <stdlib.h>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void wg_split3(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-#pragma unroll
-  for (int e = 0; e < 8; e += 2) {
-    const f32x2 x = f32x2{v[e], v[e + 1]};
-    const bf16x2 h2 = __builtin_convertvector(x, bf16x2);
-    const f32x2 r = x - __builtin_convertvector(h2, f32x2);
-    const bf16x2 m2 = __builtin_convertvector(r, bf16x2);
-    const f32x2 q = r - __builtin_convertvector(m2, f32x2);
-    const bf16x2 l2 = __builtin_convertvector(q, bf16x2);
-    h[e] = h2[0]; h[e + 1] = h2[1];
-    m[e] = m2[0]; m[e + 1] = m2[1];
-    l[e] = l2[0]; l[e + 1] = l2[1];
-  }
-}
 
 struct WgGeo {
   int tilesX, tilesY, ntiles, per_xcd;
@@ -128,7 +107,7 @@ __global__ void __launch_bounds__(256, 2) lds3_wgrad16_kernel(const IgemmParams 
       for (int e = 0; e < 4; ++e) {
         const float v[8] = {vg[0][e], vg[1][e], vg[2][e], vg[3][e], vg[4][e], vg[5][e], vg[6][e], vg[7][e]};
         bf16x8 h, m, l;
-        wg_split3(v, h, m, l);
+        split3(v, h, m, l);
         char* dst = Gp + (4 * cq + e) * WG_GSTR + pxg * 16;
         *reinterpret_cast<bf16x8*>(dst) = h;
         *reinterpret_cast<bf16x8*>(dst + WG_GPIECE) = m;
@@ -141,7 +120,7 @@ __global__ void __launch_bounds__(256, 2) lds3_wgrad16_kernel(const IgemmParams 
       for (int e = 0; e < 4; ++e) {
         const float v[8] = {vx[0][e], vx[1][e], vx[2][e], vx[3][e], vx[4][e], vx[5][e], vx[6][e], vx[7][e]};
         bf16x8 h, m, l;
-        wg_split3(v, h, m, l);
+        split3(v, h, m, l);
         char* dst = Xp + (4 * cq + e) * WG_XSTR + row * WG_XROWB + cgp * 16;
         *reinterpret_cast<bf16x8*>(dst) = h;
         *reinterpret_cast<bf16x8*>(dst + WG_XPIECE) = m;
@@ -218,7 +197,7 @@ __global__ void __launch_bounds__(256, 2) lds3_wgrad16_kernel(const IgemmParams 
           v[e] = j < 9 ? x : 0.f;
         }
         bf16x8 b[3];
-        wg_split3(v, b[0], b[1], b[2]);
+        split3(v, b[0], b[1], b[2]);
 #pragma unroll
         for (int q = 0; q < 6; ++q) acc[9] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[AS[q]], b[BS[q]], acc[9], 0, 0, 0);
       }
@@ -324,7 +303,7 @@ __global__ void __launch_bounds__(256, 2) lds3_wgrad_stem_kernel(const IgemmPara
     for (int e = 0; e < 4; ++e) {
       const float v[8] = {vg[0][e], vg[1][e], vg[2][e], vg[3][e], vg[4][e], vg[5][e], vg[6][e], vg[7][e]};
       bf16x8 h, m, l;
-      wg_split3(v, h, m, l);
+      split3(v, h, m, l);
       char* dst = Gp + (4 * cq + e) * WS_GSTR + pxg * 16;
       *reinterpret_cast<bf16x8*>(dst) = h;
       *reinterpret_cast<bf16x8*>(dst + WS_GPIECE) = m;
@@ -370,7 +349,7 @@ __global__ void __launch_bounds__(256, 2) lds3_wgrad_stem_kernel(const IgemmPara
           const float x = Ip[r * WS_ICOLS + 8 * g + e + ioff[nt]];
           v[e] = ilive[nt] ? x : 0.f;
         }
-        wg_split3(v, b[nt][0], b[nt][1], b[nt][2]);
+        split3(v, b[nt][0], b[nt][1], b[nt][2]);
       }
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -626,7 +605,7 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
     for (int e = 0; e < 4; ++e) {
       const float f[8] = {v[0][e], v[1][e], v[2][e], v[3][e], v[4][e], v[5][e], v[6][e], v[7][e]};
       bf16x8 h, m, l;
-      wg_split3(f, h, m, l);
+      split3(f, h, m, l);
       char* dst = Xp + (4 * quad + e) * WK_XSTR + row * WG_XROWB + cgp * 16;
       *reinterpret_cast<bf16x8*>(dst) = h;
       *reinterpret_cast<bf16x8*>(dst + WK_XPIECE) = m;
@@ -643,7 +622,7 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
       for (int e = 0; e < 4; ++e) {
         const float f[8] = {vb[0][e], vb[1][e], vb[2][e], vb[3][e], vb[4][e], vb[5][e], vb[6][e], vb[7][e]};
         bf16x8 h, m, l;
-        wg_split3(f, h, m, l);
+        split3(f, h, m, l);
         char* dst = Gp + (4 * cq + e) * WK_GSTR + pxg * 16;
         *reinterpret_cast<bf16x8*>(dst) = h;
         *reinterpret_cast<bf16x8*>(dst + WK_GPIECE) = m;
@@ -735,7 +714,7 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
             v[e] = j < 9 ? x : 0.f;
           }
           bf16x8 b[3];
-          wg_split3(v, b[0], b[1], b[2]);
+          split3(v, b[0], b[1], b[2]);
 #pragma unroll
           for (int q = 0; q < 6; ++q)
 #pragma unroll

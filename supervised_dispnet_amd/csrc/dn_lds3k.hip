@@ -9,63 +9,9 @@
 // meet in LDS (over the input planes, which are dead by then) and each wave of the group finishes a share of the pixel tiles.
 #include <stdlib.h>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float lk_act(float v, int act, float p0, float p1) {
-  switch (act) {
-    case DN_ACT_RELU: return v > 0.f ? v : 0.f;
-    case DN_ACT_LEAKY: return v > 0.f ? v : v * p0;
-    case DN_ACT_ELU: return v > 0.f ? v : (expf(v) - 1.f);
-    case DN_ACT_SIGMOID_AFFINE: return p0 / (1.f + expf(-v)) + p1;
-    default: return v;
-  }
-}
-
-__device__ __forceinline__ f32x4 lk_act4(f32x4 v, int act, float p0, float p1) {           // one wave-uniform branch for four values
-  f32x4 r = v;
-  switch (act) {
-    case DN_ACT_RELU:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : 0.f;
-      break;
-    case DN_ACT_LEAKY:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : v[e] * p0;
-      break;
-    case DN_ACT_ELU:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : (expf(v[e]) - 1.f);
-      break;
-    case DN_ACT_SIGMOID_AFFINE:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = p0 / (1.f + expf(-v[e])) + p1;
-      break;
-    default: break;
-  }
-  return r;
-}
-
-__device__ __forceinline__ void lk_split3(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-#pragma unroll
-  for (int e = 0; e < 8; e += 2) {
-    const f32x2 x = f32x2{v[e], v[e + 1]};
-    const bf16x2 h2 = __builtin_convertvector(x, bf16x2);
-    const f32x2 r = x - __builtin_convertvector(h2, f32x2);
-    const bf16x2 m2 = __builtin_convertvector(r, bf16x2);
-    const f32x2 q = r - __builtin_convertvector(m2, f32x2);
-    const bf16x2 l2 = __builtin_convertvector(q, bf16x2);
-    h[e] = h2[0]; h[e + 1] = h2[1];
-    m[e] = m2[0]; m[e + 1] = m2[1];
-    l[e] = l2[0]; l[e + 1] = l2[1];
-  }
-}
 
 struct LkGeo {
   int tilesX, tilesY, ntiles, per_xcd;
@@ -140,7 +86,7 @@ __global__ void __launch_bounds__(512, 2) lds3k_conv_kernel(const IgemmParams p,
           if (t0 + e < ntaps) v[e] = wrow[kbs + t0 + e];
       }
       boff[ks] = off;
-      lk_split3(v, wa[ks][0], wa[ks][1], wa[ks][2]);
+      split3(v, wa[ks][0], wa[ks][1], wa[ks][2]);
     }
   }
   int doff[8];
@@ -238,7 +184,7 @@ __global__ void __launch_bounds__(512, 2) lds3k_conv_kernel(const IgemmParams p,
         const int idx = STRIDE == 2 ? ((col & 1) * Cfg::HALFC + (col >> 1)) : col;
         const float v[8] = {va[r][0], va[r][1], va[r][2], va[r][3], vb[r][0], vb[r][1], vb[r][2], vb[r][3]};
         bf16x8 h, m, l;
-        lk_split3(v, h, m, l);
+        split3(v, h, m, l);
         char* dst = lds + cg * Cfg::CGSTRIDE + (row * Cfg::COLSP + idx) * 16;
         *reinterpret_cast<bf16x8*>(dst) = h;
         *reinterpret_cast<bf16x8*>(dst + Cfg::PSTRIDE) = m;
@@ -266,17 +212,16 @@ __global__ void __launch_bounds__(512, 2) lds3k_conv_kernel(const IgemmParams p,
     const int gy = gy0 + ty, gx = gx0 + tx16 * 16 + j;
     const int oy = gy * p.osy + ph.ooy, ox = gx * p.osx + ph.oox;
     if (fast_out) {
-      typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
       const bool ok = gy < p.GH && gx < p.GW && oy < p.OH && ox < p.OW && n0 < p.Ntot;
-      const f32x4 w4 = lk_act4(a + f32x4{bias[0], bias[1], bias[2], bias[3]}, p.act, p.act_p0, p.act_p1);
+      const f32x4 w4 = apply_act4(a + f32x4{bias[0], bias[1], bias[2], bias[3]}, p.act, p.act_p0, p.act_p1);
       const int off = (n * (int)R0.sn + oy * (int)R0.sh + (gx0 + tx16 * 16) * p.osx * (int)R0.sw + ph.oox * (int)R0.sw) * 4 + lane_out;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, w4), rout, ok ? off : -1, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w4), rout, ok ? off : -1, 0, 0);
       return;
     }
     if (gy < p.GH && gx < p.GW && oy < p.OH && ox < p.OW && n0 < p.Ntot) {
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = lk_act(a[e] + bias[e], p.act, p.act_p0, p.act_p1);
+      for (int e = 0; e < 4; ++e) v[e] = apply_act(a[e] + bias[e], p.act, p.act_p0, p.act_p1);
       if (vec_store) {
         f32x4* o = reinterpret_cast<f32x4*>(R.p + (long long)n * R.sn + (long long)oy * R.sh + (long long)ox * R.sw + cl);
         f32x4 w4 = f32x4{v[0], v[1], v[2], v[3]};
@@ -351,7 +296,7 @@ __global__ void __launch_bounds__(512, 2) lds3k_conv_kernel(const IgemmParams p,
                 v[e] = (t0 + e < ntaps) ? x : 0.f;
               }
               bf16x8 h, m, l;
-              lk_split3(v, h, m, l);
+              split3(v, h, m, l);
               if (4 * (kq * NKS + ks) + g >= nslots) { b[u][0] = h; b[u][1] = m; b[u][2] = l; }
             }
           }

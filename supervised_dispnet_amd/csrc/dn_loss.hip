@@ -1,17 +1,11 @@
 // Per-pixel depth losses and metrics (reference: loss_functions.py).  HBM/latency-bound reductions; wavefront (64-lane)
 // shuffles for the spatial reductions, no float atomics (deterministic), no host synchronisation.
 #include "dn_fold.h"
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
 
 constexpr int kLossThreads = 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // block-wide sum of NV values per thread; result valid in thread 0
 template <int NV>

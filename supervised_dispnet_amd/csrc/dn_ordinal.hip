@@ -2,15 +2,9 @@
 // utils.py:106-175).  HBM-bound: each kernel streams the 2K-channel logits / K-channel probabilities once.
 // Integer results (decode_c, SID labels) are produced with correctly-rounded double-precision transcendentals rounded to
 // float at each step of the reference's float32 expression, so they reproduce torch-CPU's integers.
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-__device__ __forceinline__ float wsum_o(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // pre: logits, element (n, pixel p, channel c) at pre[n*sn + p*sp + c*sc] (NHWC from the conv epilogue: sp = 2K, sc = 1; a
 // user NCHW tensor: sp = 1, sc = HW); channel 2k = "A", 2k+1 = "B".  ord: planar [N][K][HW] = softmax(clamp(A), clamp(B))[1].
@@ -91,8 +85,8 @@ __global__ void __launch_bounds__(256) ordinal_loss_fwd_kernel(const float* __re
       s += logf(fminf(fmaxf(v, 1e-8f), 1e8f));
     }
   }
-  s = wsum_o(s);
-  c = wsum_o(c);
+  s = wave_sum(s);
+  c = wave_sum(c);
   __shared__ float lds[8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { lds[wave] = s; lds[4 + wave] = c; }

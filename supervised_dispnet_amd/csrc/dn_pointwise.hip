@@ -2,12 +2,10 @@
 // activation backward with bias-gradient column sums, 1-channel upsamples, reciprocal, Adam.  gfx950 only.
 // All column reductions are two-stage (per-block partial rows in a caller workspace, then a finalize) so results are
 // deterministic and no float atomics are used.
-#include "dn_internal.h"
+#include "dn_device.h"
 #include "dn_fold.h"
 
 namespace dn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 constexpr int kMaxReduceBlocks = 4096;
@@ -763,14 +761,6 @@ __global__ void upsample2x_nearest_bwd_nhwc_kernel(const float* __restrict__ dfu
     if (accumulate) s += dlow[i];
     dlow[i] = s;
   }
-}
-
-__device__ __forceinline__ int reflect_idx(int v, int n) {
-  const int m = n - 1;
-  int a = v < 0 ? -v : v;
-  a = m - a;
-  a = a < 0 ? -a : a;
-  return m - a;
 }
 
 // dx[n][y][x][c] (+)= sum over padded (py, px) in [-pad, H+pad) x [-pad, W+pad) with reflect(py) == y, reflect(px) == x

@@ -13,66 +13,9 @@
 //     (per wave about a pivot, DPP row sums, two waves merged per 128-pixel row).
 #include <stdlib.h>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void sk_split3(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-#pragma unroll
-  for (int e = 0; e < 8; e += 2) {
-    const f32x2 x = f32x2{v[e], v[e + 1]};
-    const bf16x2 h2 = __builtin_convertvector(x, bf16x2);
-    const f32x2 r = x - __builtin_convertvector(h2, f32x2);
-    const bf16x2 m2 = __builtin_convertvector(r, bf16x2);
-    const f32x2 q = r - __builtin_convertvector(m2, f32x2);
-    const bf16x2 l2 = __builtin_convertvector(q, bf16x2);
-    h[e] = h2[0]; h[e + 1] = h2[1];
-    m[e] = m2[0]; m[e + 1] = m2[1];
-    l[e] = l2[0]; l[e + 1] = l2[1];
-  }
-}
-
-__device__ __forceinline__ f32x4 sk_act4(f32x4 v, int act, float p0, float p1) {
-  f32x4 r = v;
-  switch (act) {
-    case DN_ACT_RELU:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : 0.f;
-      break;
-    case DN_ACT_LEAKY:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : v[e] * p0;
-      break;
-    case DN_ACT_ELU:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = v[e] > 0.f ? v[e] : (expf(v[e]) - 1.f);
-      break;
-    case DN_ACT_SIGMOID_AFFINE:
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = p0 / (1.f + expf(-v[e])) + p1;
-      break;
-    default: break;
-  }
-  return r;
-}
-
-template <int ROT>
-__device__ __forceinline__ float sk_row_ror(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + ROT, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sk_row16_sum(float v) {
-  v += sk_row_ror<8>(v);
-  v += sk_row_ror<4>(v);
-  v += sk_row_ror<2>(v);
-  v += sk_row_ror<1>(v);
-  return v;
-}
 
 struct SkGeo {
   int tilesX, tilesY, ntiles, per_xcd;
@@ -129,7 +72,7 @@ __global__ void __launch_bounds__(512, 1) stemk_conv_kernel(const IgemmParams p,
       for (int s = 0; s < 7; ++s) v[1 + s] = wrow[(7 * r + s) * Cop + c];
     }
     bf16x8 h, mm, lo;
-    sk_split3(v, h, mm, lo);
+    split3(v, h, mm, lo);
     wl[((m * NKS + ks) * 3 + 0) * 64 + l] = h;
     wl[((m * NKS + ks) * 3 + 1) * 64 + l] = mm;
     wl[((m * NKS + ks) * 3 + 2) * 64 + l] = lo;
@@ -222,7 +165,7 @@ __global__ void __launch_bounds__(512, 1) stemk_conv_kernel(const IgemmParams p,
           const f32x2* src = reinterpret_cast<const f32x2*>(pl + boff + pbase[u]);
           const f32x2 x0 = src[0], x1 = src[1], x2 = src[2], x3 = src[3];
           const float v[8] = {x0[0], x0[1], x1[0], x1[1], x2[0], x2[1], x3[0], x3[1]};
-          sk_split3(v, b[u][0], b[u][1], b[u][2]);
+          split3(v, b[u][0], b[u][1], b[u][2]);
         }
         bf16x8 a[MT][3];
 #pragma unroll
@@ -266,8 +209,8 @@ __global__ void __launch_bounds__(512, 1) stemk_conv_kernel(const IgemmParams p,
         const int off = tbase + (ty * (int)R.sh + tx16 * 16 * (int)R.sw) * 4 + lane_out;
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-          const f32x4 w4 = sk_act4(acc[u][m] + f32x4{bias[m][0], bias[m][1], bias[m][2], bias[m][3]}, p.act, p.act_p0, p.act_p1);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, w4), rout, off + 64 * m, 0, 0);
+          const f32x4 w4 = apply_act4(acc[u][m] + f32x4{bias[m][0], bias[m][1], bias[m][2], bias[m][3]}, p.act, p.act_p0, p.act_p1);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w4), rout, off + 64 * m, 0, 0);
         }
       }
     }
@@ -278,7 +221,7 @@ __global__ void __launch_bounds__(512, 1) stemk_conv_kernel(const IgemmParams p,
         for (int m = 0; m < MT; ++m)
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float s1 = sk_row16_sum(sv[m][e]), q1 = sk_row16_sum(qv[m][e]);
+            const float s1 = row16_sum(sv[m][e]), q1 = row16_sum(qv[m][e]);
             if (j == 0)
               *reinterpret_cast<f32x2*>(&wstat[((wave * MT + m) * 16 + 4 * g + e) * 2]) = f32x2{fmaf(64.f, pv[m][e], s1), q1 - s1 * s1 * (1.f / 64.f)};
           }
@@ -406,7 +349,7 @@ __global__ void __launch_bounds__(256, 2) stemk_wgrad_kernel(const IgemmParams p
       for (int e = 0; e < 4; ++e) {
         const float v[8] = {vg[0][e], vg[1][e], vg[2][e], vg[3][e], vg[4][e], vg[5][e], vg[6][e], vg[7][e]};
         bf16x8 h, m, l;
-        sk_split3(v, h, m, l);
+        split3(v, h, m, l);
         char* dst = Gp + (4 * gq + e) * Cfg::GSTR + gpx * 16;
         *reinterpret_cast<bf16x8*>(dst) = h;
         *reinterpret_cast<bf16x8*>(dst + Cfg::GPIECE) = m;
@@ -449,7 +392,7 @@ __global__ void __launch_bounds__(256, 2) stemk_wgrad_kernel(const IgemmParams p
             v[i] = ilive[u] ? x : 0.f;
           }
           bf16x8 b[3];
-          sk_split3(v, b[0], b[1], b[2]);
+          split3(v, b[0], b[1], b[2]);
 #pragma unroll
           for (int q = 0; q < 6; ++q)
 #pragma unroll

@@ -13,11 +13,9 @@
 // four waves of a block are summed through LDS and the blocks by a second, fixed-order pass (deterministic).
 #include <stdlib.h>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThinMaxTiles = 10;
 
@@ -146,7 +144,6 @@ __global__ void __launch_bounds__(256) thin_wgrad_kernel(const IgemmParams p, co
     const int m = r * OW + x0 + pp;
     if constexpr (NTC == 4) {
       // 64 output channels: row tile i holds channels 4*col + i, so the four A values of a lane are ONE float4 of dy
-      typedef int i32x4 __attribute__((ext_vector_type(4)));
       const f32x4 a4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrcG, (m * Cout + 4 * col) * 4, 0, 0));
 #pragma unroll
       for (int i = 0; i < NTC; ++i) a[which][i] = a4[i];
@@ -266,16 +263,6 @@ int launch_thin_wgrad(IgemmParams& p, float* dw, hipStream_t stream) {
 // through a per-wave LDS tile so that they leave as whole pixels.  Driven by the same plan (taps, phases, strides) as the tiled
 // kernel and reading the same packed weights, so all four conv kinds are served.
 // =====================================================================================================================
-__device__ __forceinline__ float thin_act(float v, int act, float p0, float p1) {
-  switch (act) {
-    case DN_ACT_RELU: return v > 0.f ? v : 0.f;
-    case DN_ACT_LEAKY: return v > 0.f ? v : v * p0;
-    case DN_ACT_ELU: return v > 0.f ? v : (expf(v) - 1.f);
-    case DN_ACT_SIGMOID_AFFINE: return p0 / (1.f + expf(-v)) + p1;
-    default: return v;
-  }
-}
-
 static int thin_ksteps(const IgemmParams& p, int ntaps) {       // 4-wide MFMA k-steps of one phase
   int k4 = 0;
   for (int s = 0; s < p.n_in; ++s) k4 += (p.in[s].C % 16 == 0) ? ntaps * (p.in[s].C / 16) * 4 : (ntaps + 3) / 4;
@@ -411,7 +398,6 @@ __global__ void __launch_bounds__(256) thin_conv_kernel(const IgemmParams p, int
         for (int mt = 0; mt < 4; ++mt) base[mt] = (pn[mt] * (int)S.sn + pby[mt] * (int)S.sh + pbx[mt] * (int)S.sw + 4 * kk) * 4;
         // (tap, channel block) steps in one flat sequence, the NEXT step's four patch loads in flight under this step's 16 matrix
         // instructions (the plain nest issued them right before their first use: every step paid a full memory latency)
-        typedef int i32x4 __attribute__((ext_vector_type(4)));
         auto load_step = [&](int st, f32x4 (&dst)[4]) __attribute__((always_inline)) {
           const int j = st / nblk, cb = st - j * nblk;
           const int tp = tapl[j];
@@ -479,7 +465,7 @@ __global__ void __launch_bounds__(256) thin_conv_kernel(const IgemmParams p, int
         const int n = 16 * nt + col;
         const float bias = (p.bias != nullptr && n < p.Ntot) ? p.bias[n] : 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) tile[(4 * kk + r) * TLD + n] = thin_act(acc[mt][nt][r] + bias, p.act, p.act_p0, p.act_p1);
+        for (int r = 0; r < 4; ++r) tile[(4 * kk + r) * TLD + n] = apply_act(acc[mt][nt][r] + bias, p.act, p.act_p0, p.act_p1);
       }
       __syncthreads();
       constexpr int C4 = NP / 4;

@@ -2,22 +2,16 @@
 // All kernels are HBM / gather-latency bound: one thread per target pixel, the 3x4 projection of its sample in SGPR-like
 // uniform registers, 4-tap bilinear gather of the 3 image planes, wavefront-shuffle reductions for the per-sample pose
 // gradients and the loss sums.  No atomics (deterministic), no host synchronisation.
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // block-wide sum of NV per-thread values into out[0..NV) by thread 0 (256-thread blocks)
 template <int NV>
 __device__ __forceinline__ void block_sum256(float (&v)[NV], float* lds /* [NV*4] */, float* out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = wsum(v[i]);
+  for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
   __syncthreads();
   if (lane == 0)
 #pragma unroll

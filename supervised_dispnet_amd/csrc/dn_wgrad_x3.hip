@@ -11,46 +11,9 @@
 // Everything around it -- pixel splits filling whole rounds, XCD-aware tile order, the fixed-order split sum -- is the fp32 kernel's.
 #include <stdlib.h>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void wx_split3(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-#pragma unroll
-  for (int e = 0; e < 8; e += 2) {
-    const f32x2 x = f32x2{v[e], v[e + 1]};
-    const bf16x2 h2 = __builtin_convertvector(x, bf16x2);
-    const f32x2 r = x - __builtin_convertvector(h2, f32x2);
-    const bf16x2 m2 = __builtin_convertvector(r, bf16x2);
-    const f32x2 q = r - __builtin_convertvector(m2, f32x2);
-    const bf16x2 l2 = __builtin_convertvector(q, bf16x2);
-    h[e] = h2[0]; h[e + 1] = h2[1];
-    m[e] = m2[0]; m[e + 1] = m2[1];
-    l[e] = l2[0]; l[e + 1] = l2[1];
-  }
-}
-
-__device__ __forceinline__ int wx_select_operand(const IgemmParams& p, int ntaps, int kc, int* kc_local) {
-  int s = 0;
-#pragma unroll
-  for (int i = 0; i < DN_MAX_OPERANDS - 1; ++i) {
-    if (s == i && i < p.n_in - 1) {
-      const int nch = (ntaps * p.in[i].C + kChunk - 1) / kChunk;
-      if (kc >= nch) {
-        kc -= nch;
-        s = i + 1;
-      }
-    }
-  }
-  *kc_local = kc;
-  return s;
-}
 
 constexpr int WX_ROWB = 80;          // bytes of one channel row: 32 pixels x bf16 + 16 (bank stagger)
 
@@ -94,7 +57,7 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_x3_kernel(const IgemmParam
     const int kc = kt * 4 + q;
     int kcl = 0;
     const bool chunk_live = kc < nchunks;
-    const int s = chunk_live ? wx_select_operand(p, ntaps, kc, &kcl) : 0;
+    const int s = chunk_live ? select_operand(p, ntaps, kc, &kcl) : 0;
     const KOperand& S = p.in[s];
     unsigned c;
     const int j = (int)fastdiv_dev((unsigned)(kcl * kChunk + g8 * 4), (unsigned)S.C, S.mC, &c);
@@ -171,7 +134,7 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_x3_kernel(const IgemmParam
           f[i] = (okmask >> i) & 1u ? t : 0.f;
         }
         bf16x8 h, m, l;
-        wx_split3(f, h, m, l);
+        split3(f, h, m, l);
         char* dst = lds + (chrow + e) * WX_ROWB + pg * 16;
         *reinterpret_cast<bf16x8*>(dst) = h;
         *reinterpret_cast<bf16x8*>(dst + PIECE) = m;

@@ -31,7 +31,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 #include "dn_wino_common.h"
 
 namespace dn {
@@ -186,13 +186,6 @@ int launch_wino_pack_many(const PackEntry* tab_dev, int first, int n, hipStream_
 //   NSPL = 1 (DN_COMPUTE_BF16) : piece_0 = U rounded to bf16 (nearest even)
 //   NSPL = 3 (DN_COMPUTE_F32X3): U = piece_0 + piece_1 + piece_2 EXACTLY (each piece the bf16 rounding of what the previous ones left;
 //                                3 x 8 significant bits hold any fp32 value)
-__device__ __forceinline__ void wino_split3(float x, __bf16* pc) {
-  pc[0] = (__bf16)x;
-  const float r1 = x - (float)pc[0];        // exact (Sterbenz), at most 16 significant bits
-  pc[1] = (__bf16)r1;
-  pc[2] = (__bf16)(r1 - (float)pc[1]);      // exact, at most 8 significant bits: the conversion does not round
-}
-
 template <int NSPL>
 __device__ __forceinline__ void wino_pack16_body(const IgemmParams& p, const float* __restrict__ w, float* __restrict__ wp, int NS, long long total) {
   __bf16* wp16 = reinterpret_cast<__bf16*>(wp);
@@ -209,19 +202,17 @@ __device__ __forceinline__ void wino_pack16_body(const IgemmParams& p, const flo
   }
   // one thread per (n, k PAIR): two adjacent k share every store (one dword = two bf16) and every conversion (v_cvt_pk_bf16_f32 takes
   // two values) -- half the stores, conversions and address arithmetic per weight of the one-thread-per-(n, k) form (round 5)
-  typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-  typedef float f32x2v __attribute__((ext_vector_type(2)));
   const long long nduos = total >> 5;
   for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < nduos; idx += (long long)gridDim.x * blockDim.x) {
     const int e2 = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
     const long long rest = idx >> 8;
     const int nsub = (int)(rest % NS), kc16 = (int)(rest / NS);
     const int k0 = kc16 * 16 + (lane >> 5) * 8 + 2 * e2, n = nsub * 32 + (lane & 31);
-    f32x2v g[3][3];
+    f32x2 g[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
-      for (int b = 0; b < 3; ++b) g[a][b] = f32x2v{0.f, 0.f};
+      for (int b = 0; b < 3; ++b) g[a][b] = f32x2{0.f, 0.f};
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int k = k0 + h;
@@ -242,10 +233,10 @@ __device__ __forceinline__ void wino_pack16_body(const IgemmParams& p, const flo
           for (int bb = 0; bb < 3; ++bb) g[aa][bb][h] = w[base + src_of[aa * 3 + bb]];
       }
     }
-    f32x2v t4[4][3];
+    f32x2 t4[4][3];
 #pragma unroll
     for (int bb = 0; bb < 3; ++bb) {
-      const f32x2v g0 = g[0][bb], g1 = g[1][bb], g2 = g[2][bb];
+      const f32x2 g0 = g[0][bb], g1 = g[1][bb], g2 = g[2][bb];
       t4[0][bb] = g0;
       t4[1][bb] = 0.5f * (g0 + g1 + g2);
       t4[2][bb] = 0.5f * (g0 - g1 + g2);
@@ -255,7 +246,7 @@ __device__ __forceinline__ void wino_pack16_body(const IgemmParams& p, const flo
     const long long posB = (long long)NS * NSPL * 64 * 8;     // elements between two positions
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      f32x2v u[4];
+      f32x2 u[4];
       u[0] = t4[i][0];
       u[1] = 0.5f * (t4[i][0] + t4[i][1] + t4[i][2]);
       u[2] = 0.5f * (t4[i][0] - t4[i][1] + t4[i][2]);
@@ -263,17 +254,17 @@ __device__ __forceinline__ void wino_pack16_body(const IgemmParams& p, const flo
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         // the same three-piece split as wino_split3, two values at a time: piece = bf16(what the previous pieces left), exactly
-        const bf16x2v p0 = __builtin_convertvector(u[j], bf16x2v);
+        const bf16x2 p0 = __builtin_convertvector(u[j], bf16x2);
         if constexpr (NSPL == 1) {
-          *reinterpret_cast<bf16x2v*>(dst + (4 * i + j) * posB) = p0;
+          *reinterpret_cast<bf16x2*>(dst + (4 * i + j) * posB) = p0;
         } else {
-          const f32x2v r1 = u[j] - __builtin_convertvector(p0, f32x2v);
-          const bf16x2v p1 = __builtin_convertvector(r1, bf16x2v);
-          const f32x2v r2 = r1 - __builtin_convertvector(p1, f32x2v);
-          const bf16x2v p2 = __builtin_convertvector(r2, bf16x2v);
-          *reinterpret_cast<bf16x2v*>(dst + (4 * i + j) * posB) = p0;
-          *reinterpret_cast<bf16x2v*>(dst + (4 * i + j) * posB + 512) = p1;
-          *reinterpret_cast<bf16x2v*>(dst + (4 * i + j) * posB + 1024) = p2;
+          const f32x2 r1 = u[j] - __builtin_convertvector(p0, f32x2);
+          const bf16x2 p1 = __builtin_convertvector(r1, bf16x2);
+          const f32x2 r2 = r1 - __builtin_convertvector(p1, f32x2);
+          const bf16x2 p2 = __builtin_convertvector(r2, bf16x2);
+          *reinterpret_cast<bf16x2*>(dst + (4 * i + j) * posB) = p0;
+          *reinterpret_cast<bf16x2*>(dst + (4 * i + j) * posB + 512) = p1;
+          *reinterpret_cast<bf16x2*>(dst + (4 * i + j) * posB + 1024) = p2;
         }
       }
     }
@@ -877,7 +868,6 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
           for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-              typedef int i32x4 __attribute__((ext_vector_type(4)));
               const i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rws, (int)(((z * 8 + (k * 2 + a) * 2 + b) * 256 + tid) * 16), 0, 1 /* glc */);
               Y[k][a][b] += __builtin_bit_cast(f32x4, v);
             }
@@ -1020,7 +1010,7 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
               v[a][b] = Y[k][a][b] + bias;
               if (!plain) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[a][b][e] = wino_act(v[a][b][e], p.act, p.act_p0, p.act_p1);
+                for (int e = 0; e < 4; ++e) v[a][b][e] = apply_act(v[a][b][e], p.act, p.act_p0, p.act_p1);
               }
             }
           if (accumulate) {                 // second writer of a skip connection: the four loads go out together
@@ -1059,7 +1049,7 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
               for (int e = 0; e < 4; ++e) {
                 const int col = n_first + e;
                 if (col < p.Ntot) {
-                  const float val = wino_act(Y[k][a][b][e] + bias[e], p.act, p.act_p0, p.act_p1);
+                  const float val = apply_act(Y[k][a][b][e] + bias[e], p.act, p.act_p0, p.act_p1);
                   int sg = 0;
                   if (p.n_out > 1 && col >= p.out[1].n_begin) sg = 1;
                   if (p.n_out > 2 && col >= p.out[2].n_begin) sg = 2;

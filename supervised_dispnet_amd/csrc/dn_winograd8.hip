@@ -20,7 +20,7 @@
 // live in a ring of six registers that is refilled in release order during the second tile half (10-12 instructions of lead).
 #include <stdlib.h>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 #include "dn_wino_common.h"
 
 namespace dn {
@@ -458,7 +458,6 @@ __global__ void __launch_bounds__(512, 1) wino_conv8_kernel(const IgemmParams p)
           for (int nn = 0; nn < 2; ++nn)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              typedef int i32x4 __attribute__((ext_vector_type(4)));
               const i32x4 vi = __builtin_amdgcn_raw_buffer_load_b128(rws, (int)(((z * 32 + ((a * 2 + m) * 2 + nn) * 4 + e) * 512 + tid) * 16), 0, 1 /* glc */);
               const f32x4 v = __builtin_bit_cast(f32x4, vi);
 #pragma unroll
@@ -661,7 +660,7 @@ __global__ void __launch_bounds__(512, 1) wino_conv8_kernel(const IgemmParams p)
               v[a][b] = Y[k][a][b] + bias;
               if (!plain) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[a][b][e] = wino_act(v[a][b][e], p.act, p.act_p0, p.act_p1);
+                for (int e = 0; e < 4; ++e) v[a][b][e] = apply_act(v[a][b][e], p.act, p.act_p0, p.act_p1);
               }
             }
           if (accumulate) {                 // second writer of a skip connection: the four loads go out together
@@ -698,7 +697,7 @@ __global__ void __launch_bounds__(512, 1) wino_conv8_kernel(const IgemmParams p)
               for (int e = 0; e < 4; ++e) {
                 const int col = n_first + e;
                 if (col < p.Ntot) {
-                  const float val = wino_act(Y[k][a][b][e] + bias[e], p.act, p.act_p0, p.act_p1);
+                  const float val = apply_act(Y[k][a][b][e] + bias[e], p.act, p.act_p0, p.act_p1);
                   int sg = 0;
                   if (p.n_out > 1 && col >= p.out[1].n_begin) sg = 1;
                   if (p.n_out > 2 && col >= p.out[2].n_begin) sg = 2;

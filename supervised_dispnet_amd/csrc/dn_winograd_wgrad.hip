@@ -22,21 +22,9 @@
 #include <type_traits>
 #include <utility>
 
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <class F, int... I>
-__device__ __forceinline__ void wg_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void wg_static_for(F&& f) {
-  wg_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 constexpr int GTC = 8;                        // tiles per chunk
 constexpr int G_ROWB = 64 * 4;                // one tile row: 64 channels
@@ -44,12 +32,6 @@ constexpr int G_PLANE = GTC * G_ROWB;         // one position: [8 tiles][64 chan
 constexpr int G_OPB = 16 * G_PLANE;           // one operand (G or V) of one buffer = 32 KiB
 constexpr int G_BUFB = 2 * G_OPB;             // G then V
 constexpr size_t kWgLds = (size_t)2 * G_BUFB; // 128 KiB
-
-__device__ __forceinline__ f32x4 wg_buffer_load(__amdgpu_buffer_rsrc_t r, int voffset) {
-  typedef int i32x4 __attribute__((ext_vector_type(4)));
-  const i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voffset, 0, 0);
-  return __builtin_bit_cast(f32x4, v);
-}
 
 bool wino_wgrad_eligible(const dn_conv_desc* d, const IgemmParams& p) {
   if (knobs().no_winograd || knobs().no_winograd_wgrad) return false;
@@ -136,17 +118,8 @@ __global__ void wino_wgrad_fold_kernel(const float* __restrict__ ws, float* __re
   }
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ f32x2 wg_buffer_load2s(__amdgpu_buffer_rsrc_t r, int voffset, int soffset) {      // soffset: wave-uniform
-  typedef int i32x2 __attribute__((ext_vector_type(2)));
   const i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voffset, soffset, 0);
-  return __builtin_bit_cast(f32x2, v);
-}
-
-__device__ __forceinline__ f32x2 wg_buffer_load2(__amdgpu_buffer_rsrc_t r, int voffset) {
-  typedef int i32x2 __attribute__((ext_vector_type(2)));
-  const i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voffset, 0, 0);
   return __builtin_bit_cast(f32x2, v);
 }
 
@@ -238,7 +211,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
       int off = off0 + (i >> 2) * shB + (i & 3) * swB;
       asm volatile("" : "+v"(off));
       off = ((pm >> i) & 1u) ? off : -1;
-      v[i] = wg_buffer_load2(rsrcX, off);
+      v[i] = buffer_load_vec<2>(rsrcX, off);
     }
   };
   auto load_grad = [&](int target) {
@@ -251,7 +224,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
       int off = off0 + (i >> 1) * growB + (i & 1) * gpixB;
       asm volatile("" : "+v"(off));
       off = live ? off : -1;
-      gv[i] = wg_buffer_load2(rsrcG, off);
+      gv[i] = buffer_load_vec<2>(rsrcG, off);
     }
   };
   auto affine_piece = [&](f32x2 (&v)[16], unsigned pm, int i) {
@@ -347,7 +320,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
         load_grad(c + 2);
       }
       __builtin_amdgcn_sched_barrier(0);
-      wg_static_for<32>([&](auto mc) __attribute__((always_inline)) {
+      static_for<32>([&](auto mc) __attribute__((always_inline)) {
         constexpr int m = decltype(mc)::value;
         constexpr int g = m / 4, qq = m % 4;           // g = (k-step, position): 4 MFMAs
         constexpr int pp = g & 1;
@@ -415,10 +388,6 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
 //     are needed for the operands): a wave requests its next chunk's patch + gradient tile at the top of one chunk and transforms +
 //     stores them during the next one; ONE barrier per chunk, placed after the last read of the current buffer / the last store
 //     into the next one (slot 12 of 24), so that the next chunk's first operands are built under the current chunk's tail.
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
-
 template <bool HA, int DBG = 0>     // DBG (timing ablations, wrong results): 1 no transform + stores, 2 no split arithmetic, 4 no global loads, 8 no LDS fragment reads (the split of the never-changing registers is hoisted too), 16 no LDS stores (arithmetic kept), 32 no barrier
 __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams p) {
   extern __shared__ __align__(16) float smem[];
@@ -570,7 +539,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
 
   // ---- operands of the matrix instructions: per co half h  A1 = (x0, x1), A3 = (x0, x2);  per ci half nn  B1 = (y0, y0),
   //      B2 = (y1, y1), B3 = (y2, y0): two dwords (four own tiles) of the first piece, two of the second
-  wg_u32x4 Aop[2][2], Bop[2][3];
+  u32x4 Aop[2][2], Bop[2][3];
   float raw[2][4];
   unsigned Pk[3][2];                                    // pieces of the fragment being built: [piece][tile pair]
   // build k of a chunk (3 matrix instructions each): what it produces and where it reads
@@ -592,11 +561,11 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
       P[2][hf] = __builtin_bit_cast(unsigned, x[0]) ^ 0x11u;
       return;
     }
-    const wg_bf16x2 h = __builtin_convertvector(x, wg_bf16x2);
+    const bf16x2 h = __builtin_convertvector(x, bf16x2);
     const f32x2 r1 = x - __builtin_convertvector(h, f32x2);
-    const wg_bf16x2 m = __builtin_convertvector(r1, wg_bf16x2);
+    const bf16x2 m = __builtin_convertvector(r1, bf16x2);
     const f32x2 r2 = r1 - __builtin_convertvector(m, f32x2);
-    const wg_bf16x2 l = __builtin_convertvector(r2, wg_bf16x2);
+    const bf16x2 l = __builtin_convertvector(r2, bf16x2);
     P[0][hf] = __builtin_bit_cast(unsigned, h);
     P[1][hf] = __builtin_bit_cast(unsigned, m);
     P[2][hf] = __builtin_bit_cast(unsigned, l);
@@ -610,12 +579,12 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
       split_half(k, 1, Pk);
     } else {
       if (isB) {
-        Bop[half][0] = wg_u32x4{Pk[0][0], Pk[0][1], Pk[0][0], Pk[0][1]};      // (y0, y0)
-        Bop[half][1] = wg_u32x4{Pk[1][0], Pk[1][1], Pk[1][0], Pk[1][1]};      // (y1, y1)
-        Bop[half][2] = wg_u32x4{Pk[2][0], Pk[2][1], Pk[0][0], Pk[0][1]};      // (y2, y0)
+        Bop[half][0] = u32x4{Pk[0][0], Pk[0][1], Pk[0][0], Pk[0][1]};      // (y0, y0)
+        Bop[half][1] = u32x4{Pk[1][0], Pk[1][1], Pk[1][0], Pk[1][1]};      // (y1, y1)
+        Bop[half][2] = u32x4{Pk[2][0], Pk[2][1], Pk[0][0], Pk[0][1]};      // (y2, y0)
       } else {
-        Aop[half][0] = wg_u32x4{Pk[0][0], Pk[0][1], Pk[1][0], Pk[1][1]};      // (x0, x1)
-        Aop[half][1] = wg_u32x4{Pk[0][0], Pk[0][1], Pk[2][0], Pk[2][1]};      // (x0, x2)
+        Aop[half][0] = u32x4{Pk[0][0], Pk[0][1], Pk[1][0], Pk[1][1]};      // (x0, x1)
+        Aop[half][1] = u32x4{Pk[0][0], Pk[0][1], Pk[2][0], Pk[2][1]};      // (x0, x2)
       }
     }
   };
@@ -662,12 +631,12 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
         load_grad(c + 2);
       }
       __builtin_amdgcn_sched_barrier(0);
-      wg_static_for<24>([&](auto mc) __attribute__((always_inline)) {
+      static_for<24>([&](auto mc) __attribute__((always_inline)) {
         constexpr int m = decltype(mc)::value;
         constexpr int pp = m / 12, q12 = m % 12, h = q12 / 6, nn = (q12 / 3) % 2, t = q12 % 3;
         constexpr int grp = m / 3, part = m % 3;
-        const wg_u32x4 ao = Aop[h][t == 2 ? 1 : 0], bo = Bop[nn][t];
-        acc[pp][h][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wg_bf16x8, ao), __builtin_bit_cast(wg_bf16x8, bo), acc[pp][h][nn], 0, 0, 0);
+        const u32x4 ao = Aop[h][t == 2 ? 1 : 0], bo = Bop[nn][t];
+        acc[pp][h][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ao), __builtin_bit_cast(bf16x8, bo), acc[pp][h][nn], 0, 0, 0);
         // ---- side work of this slot: finish build `grp`; its last part frees its raw values: request the reads of build grp + 2
         //      (builds 0-5 read the current buffer and are all requested by slot 11; 6, 7 and the next chunk's 0, 1 read the next
         //      buffer and are requested after the barrier of slot 14)
@@ -882,7 +851,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
   };
 
   // ---- operands: A1 = (x0, x1), A3 = (x0, x2) of 32 output channels; B1 = (y0, y0), B2 = (y1, y1), B3 = (y2, y0) of 32 input channels
-  wg_u32x4 Aop[2][2], Bop[2][3];
+  u32x4 Aop[2][2], Bop[2][3];
   float raw[4][4];
   unsigned Pk[3][2];
   // builds of a chunk: id 0 = B(nn 1), 1 = A(h 1), 2 = A(h 2), 3 = A(h 3) read the current buffer; 4 = A(h 0), 5 = B(nn 0) of the next chunk read
@@ -920,7 +889,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
         continue;
       }
       const f32x2 v2 = f32x2{x[2 * hf], x[2 * hf + 1]};
-      const wg_bf16x2 pc = __builtin_convertvector(v2, wg_bf16x2);
+      const bf16x2 pc = __builtin_convertvector(v2, bf16x2);
       Pk[level][hf] = __builtin_bit_cast(unsigned, pc);
       if (level < 2) {
         const f32x2 r = v2 - __builtin_convertvector(pc, f32x2);
@@ -934,13 +903,13 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
     if (part < 2) return;
     if (id == 0 || id == 5) {
       const int nn = id == 0 ? 1 : 0;
-      Bop[nn][0] = wg_u32x4{Pk[0][0], Pk[0][1], Pk[0][0], Pk[0][1]};      // (y0, y0)
-      Bop[nn][1] = wg_u32x4{Pk[1][0], Pk[1][1], Pk[1][0], Pk[1][1]};      // (y1, y1)
-      Bop[nn][2] = wg_u32x4{Pk[2][0], Pk[2][1], Pk[0][0], Pk[0][1]};      // (y2, y0)
+      Bop[nn][0] = u32x4{Pk[0][0], Pk[0][1], Pk[0][0], Pk[0][1]};      // (y0, y0)
+      Bop[nn][1] = u32x4{Pk[1][0], Pk[1][1], Pk[1][0], Pk[1][1]};      // (y1, y1)
+      Bop[nn][2] = u32x4{Pk[2][0], Pk[2][1], Pk[0][0], Pk[0][1]};      // (y2, y0)
     } else {
       const int a = id == 4 ? 0 : (id & 1);                                // A(h) lives in Aop[h & 1]
-      Aop[a][0] = wg_u32x4{Pk[0][0], Pk[0][1], Pk[1][0], Pk[1][1]};       // (x0, x1)
-      Aop[a][1] = wg_u32x4{Pk[0][0], Pk[0][1], Pk[2][0], Pk[2][1]};       // (x0, x2)
+      Aop[a][0] = u32x4{Pk[0][0], Pk[0][1], Pk[1][0], Pk[1][1]};       // (x0, x1)
+      Aop[a][1] = u32x4{Pk[0][0], Pk[0][1], Pk[2][0], Pk[2][1]};       // (x0, x2)
     }
   };
 
@@ -981,11 +950,11 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
       constexpr bool REQ = decltype(req_tag)::value;       // request phase (loads for chunk c + 2), else transform + store phase (chunk c + 1)
       if constexpr (REQ && !(DBG & 4)) load_chunk(c + 2);
       __builtin_amdgcn_sched_barrier(0);
-      wg_static_for<24>([&](auto mc) __attribute__((always_inline)) {
+      static_for<24>([&](auto mc) __attribute__((always_inline)) {
         constexpr int m = decltype(mc)::value;
         constexpr int h = m / 6, nn = (m / 3) % 2, t = m % 3;
-        const wg_u32x4 ao = Aop[h & 1][t == 2 ? 1 : 0], bo = Bop[nn][t];
-        acc[h][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wg_bf16x8, ao), __builtin_bit_cast(wg_bf16x8, bo), acc[h][nn], 0, 0, 0);
+        const u32x4 ao = Aop[h & 1][t == 2 ? 1 : 0], bo = Bop[nn][t];
+        acc[h][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ao), __builtin_bit_cast(bf16x8, bo), acc[h][nn], 0, 0, 0);
         // ---- side work: operand builds (three slots each) and the fragment reads that follow them
         constexpr int bid = m < 9 ? m / 3 : (m >= 12 && m < 15) ? 3 : (m >= 18 && m < 21) ? 4 : m >= 21 ? 5 : -1;
         constexpr int part = m % 3;

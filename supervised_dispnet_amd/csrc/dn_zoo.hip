@@ -2,11 +2,9 @@
 // batch statistics of a materialised tensor in the conv epilogues' partial layout, BatchNorm apply without ReLU, an element-wise
 // activation, and the one-channel bilinear resize of F.interpolate (either align_corners).  HBM / latency bound, deterministic
 // (gathers and fixed-order sums, no float atomics).
-#include "dn_internal.h"
+#include "dn_device.h"
 
 namespace dn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int kZThreads = 256;
