@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Batched depth evaluation on the KITTI Eigen split / NYU: the command line of test_disp.py plus two flags,
+"""Batched depth evaluation on the KITTI Eigen split / NYU: the command line of test_disp.py plus three flags,
 
     python3 eval_disp.py --pretrained-dispnet CKPT --network disp_vgg_BN --dataset-dir KITTI_RAW \
         --dataset-list kitti_eval/test_files_eigen.txt --eval-batch 32 --readers 16
@@ -7,6 +7,8 @@
 --eval-batch N   N images per eval-mode forward; cubic-spline zoom to each ground-truth size, clip, mask, median / x5.4 scale and the
                  seven metrics run on the device (supervised_dispnet_amd/evaluation.py).  0 (the default) hands
                  the whole run to test_disp.py's per-image host chain.
+--device-resize  with --eval-batch on KITTI: the frames are uploaded as they are and byte-scaled, resized and normalised on the device
+                 (dn_imresize_u8; bit for bit the host resize).  NYU and --no-resize keep the host path.
 --readers N      host threads (default 4, at most 16) that read framework[j] -- image, velodyne projection, mask -- ahead of the GPU.
 
 The printed lines, the returned mean errors and predictions.npy are those of test_disp.py.  --error (the worst-300-pixel report) stays
@@ -14,7 +16,7 @@ on the per-image host chain and refuses --eval-batch.  The PoseNet-scaled evalua
 plots are outside this path, as they are outside test_disp.py's.
 
 Why a script of its own: test_disp.py carries the reference's command line and is kept exactly as it is (existing files named test_*.py are
-yardsticks in this repository and a feature leaves them alone), so the two flags cannot live there.  With --eval-batch this script therefore repeats
+yardsticks in this repository and a feature leaves them alone), so these flags cannot live there.  With --eval-batch this script therefore repeats
 test_disp.main's set-up around its own loop; tests/test_gpu_eval_device.py holds the two mains to the same printed lines and results.
 """
 import os
@@ -29,6 +31,7 @@ if ROOT not in sys.path:
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 import test_disp  # noqa: E402  (the reference's command line: parser, network construction, the per-image chain)
+from supervised_dispnet_amd.evaluation import prefetched  # noqa: E402
 
 MAX_READERS = 16
 
@@ -36,13 +39,15 @@ MAX_READERS = 16
 def add_flags(p):
     p.add_argument("--eval-batch", default=0, type=int, metavar="N",
                    help="images per forward with zoom, mask, scale and metrics on the device; 0: test_disp.py's per-image host chain")
+    p.add_argument("--device-resize", action="store_true",
+                   help="with --eval-batch on KITTI: upload the raw frames and resize them on the device (dn_imresize_u8) instead of on the host")
     p.add_argument("--readers", default=4, type=int, metavar="N", help="host threads that read ahead for --eval-batch (at most 16)")
     return p
 
 
 def build_parser():
     p = add_flags(test_disp.build_parser())
-    p.allow_abbrev = False            # flags are spelled out here, so that host_chain_argv finds this script's two by the same rule
+    p.allow_abbrev = False            # flags are spelled out here, so that host_chain_argv finds this script's own by the same rule
     return p
 
 
@@ -50,6 +55,8 @@ def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     if args.eval_batch < 0:
         raise SystemExit("eval_disp.py: --eval-batch must be >= 0")
+    if args.device_resize and not args.eval_batch:
+        raise SystemExit("eval_disp.py: --device-resize belongs to the batched chain; add --eval-batch N")
     if args.eval_batch and args.error:
         raise SystemExit("eval_disp.py: --error (the worst-300-pixel report) runs on the per-image host chain; drop --eval-batch")
     args.readers = max(1, min(MAX_READERS, args.readers))
@@ -57,23 +64,9 @@ def parse_args(argv=None):
 
 
 def host_chain_argv(argv):
-    """argv without the two flags of this script (and their values): what test_disp.main takes.  argparse itself picks them out."""
+    """argv without the flags this script adds (and their values): what test_disp.main takes.  argparse itself picks them out."""
     import argparse
     return add_flags(argparse.ArgumentParser(add_help=False, allow_abbrev=False)).parse_known_args(list(argv))[1]
-
-
-def prefetched(framework, n, readers, ahead):
-    """framework[0], framework[1], ... in order, read by `readers` threads up to `ahead` items in front of the consumer."""
-    import collections
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=readers) as pool:
-        pending = collections.deque()
-        nxt = 0
-        for _ in range(n):
-            while nxt < n and len(pending) < ahead:
-                pending.append(pool.submit(framework.__getitem__, nxt))
-                nxt += 1
-            yield pending.popleft().result()
 
 
 def evaluate_batched(args, disp_net, framework, device, min_depth, max_depth):
@@ -133,7 +126,7 @@ def main(argv=None):
                 test_files = f.read().splitlines()
         else:
             test_files = sorted(n for n in os.listdir(args.dataset_dir) if n.split(".")[-1] in args.img_exts)
-        framework = KE.KittiTestFramework(args.dataset_dir, test_files, min_depth=min_depth, max_depth=max_depth)
+        framework = KE.KittiTestFramework(args.dataset_dir, test_files, min_depth=min_depth, max_depth=max_depth, keep_u8=args.device_resize)
     else:
         min_depth, max_depth = 1e-3, 10
         framework = KE.NyuTestFramework(args.dataset_dir, min_depth=min_depth, max_depth=max_depth)

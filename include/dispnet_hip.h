@@ -615,6 +615,37 @@ int dn_eval_errors(const float* gt, const float* pred, const uint8_t* mask, cons
                    int32_t scale_mode, float fixed_scale, float* out, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Image arithmetic around the network (reference run_inference.py:121-183, utils.py:45-76).  Equality with the
+ * host libraries is the contract: every step is integer or fixed fp32 / fp64 arithmetic.
+ * dn_imresize_u8 = scipy.misc.imresize(frame, (h, w)) for a ragged batch of RGB uint8 frames: frame b is H_b x W_b x 3 bytes at byte offset
+ * off[b] of `frames`; hw = int32[B][2] {H_b, W_b} and off = int64[B] on the device.  A frame that already is h x w is passed through.
+ * Otherwise: byte-scale by the frame's min / max over all channels, uint8(clip(fp32((fp32(a) - cmin) * fp32(255.0 / (cmax - cmin))) + 0.5f,
+ * 0, 255)) (scale 1 for a constant frame), then Pillow's 8-bit bilinear resize: the horizontal pass into uint8, then the vertical pass, a
+ * pass whose axis keeps its size skipped; out = clip8((2^21 + sum k_x * in_x) >> 22).  The coefficients come from the host: `tabs` is a pool
+ * of int32 tables on the device, one per resized axis, [O][2 + T] = {first input index, taps, k[T]} per output index (T = the table's
+ * largest tap count, unused k are 0), and tab_idx = int32[B][4] {x table offset, its T, y table offset, its T} (in int32 elements; T = 0 for
+ * an axis that keeps its size).  max_taps = the largest T: more than DN_IMRESIZE_MAX_TAPS is DN_ERR_BAD_ARG, never a truncated filter.
+ * minmax = int32[B][DN_IMAGE_CHUNKS][2] workspace.  Outputs are dense and either may be NULL: out_u8 = uint8[B][h][w][3], out_f32 =
+ * fp32[B][3][h][w] = (u8 / 255 - mean[c]) / std[c] in IEEE fp32, bit-identical to dn_u8_normalize_flip(flip = NULL) of out_u8
+ * (mean_host / std_host: 3 floats each on the host).
+ * dn_colorize_u8 = 255 * tensor2array(x[b, r0:r1, c0:c1]) as uint8[B][r1-r0][c1-c0][3] of fp32 maps x[B][h][w]; reciprocal != 0 colours
+ * 1 / x (one IEEE division).  max_value < 0: the per-image maximum over the rectangle (max_ws = float[B][DN_IMAGE_CHUNKS], a NaN wins).
+ * table = uint8[256][3] RGB on the device: index uint8(clip(fp32(fp32(255 * x) / max), 0, 255)), truncating; table = NULL: the grey
+ * branch, uint8(fp32(255 * clip(fp32(x / max), 0, 1))) in all three channels.  A NaN (inf / inf) gives index / grey 0.
+ * dn_contrast_u8 = PIL.ImageEnhance.Contrast(im).enhance(factor) on uint8[B][h][w][3]: L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16,
+ * m = int(sum(L) / (h * w) + 0.5) (integer sum, one fp64 division), out = uint8(clip(fp32(m) + factor * (fp32(p) - fp32(m)), 0, 255)).
+ * sum_ws = uint64[B][DN_IMAGE_CHUNKS] workspace; src != dst.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DN_IMAGE_CHUNKS 64
+#define DN_IMRESIZE_MAX_TAPS 32
+int dn_imresize_u8(const uint8_t* frames, const int32_t* hw, const int64_t* off, int32_t B, int32_t h, int32_t w, const int32_t* tabs,
+                   const int32_t* tab_idx, int32_t max_taps, int32_t* minmax, uint8_t* out_u8, const float* mean_host, const float* std_host,
+                   float* out_f32, dn_stream_t stream);
+int dn_colorize_u8(const float* x, int32_t B, int32_t h, int32_t w, int32_t r0, int32_t r1, int32_t c0, int32_t c1, int32_t reciprocal,
+                   float max_value, const uint8_t* table, float* max_ws, uint8_t* out, dn_stream_t stream);
+int dn_contrast_u8(const uint8_t* src, int32_t B, int32_t h, int32_t w, float factor, uint64_t* sum_ws, uint8_t* dst, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Attainable-peak probes (SURVEY.md section 8d "Peaks"; used by bench.py only): a float4 streaming copy of n floats
  * (n % 4 == 0, 16-byte aligned; moves 8*n bytes) and a register-resident v_mfma_f32_32x32x2_f32 loop
  * (out: blocks*256 floats; dn_ubench_mfma_f32_flops = the FLOPs one launch executes).

@@ -1,5 +1,6 @@
 """Batched evaluation of test_disp.py's chain on the device (eval_disp.py --eval-batch): everything between the
-resized input frames and the seven error numbers of an image stays on the GPU.
+resized input frames and the seven error numbers of an image stays on the GPU -- with --device-resize (KITTI) the resize too: the raw
+frames are uploaded and dn_imresize_u8 writes the normalised batch, bit for bit what the host path uploads.
 
 Per batch the host does what test_disp.evaluate_sample does before the forward (scipy.misc.imresize semantics, transpose) and packs
 ground truth and masks; the device normalises, runs ONE eval-mode forward at batch B, takes 1/disp (or the SID decode), and then
@@ -86,12 +87,37 @@ def prepare_frame(args, sample):
     return np.ascontiguousarray(tgt, dtype=np.float32)
 
 
+def raw_frame(sample):
+    """The frame as the file holds it, uint8 [H, W, 3], for --device-resize: sample["tgt_u8"] where the framework kept it, else
+    sample["tgt"] cast back (refused unless that is exact: the device byte-scales integers)."""
+    u8 = sample.get("tgt_u8")
+    if u8 is None:
+        u8 = sample["tgt"].astype(np.uint8)
+        if not np.array_equal(u8, sample["tgt"]):
+            raise ValueError("--device-resize takes frames with integer values 0 ... 255")
+    return u8
+
+
 def sample_ground_truth(args, sample, min_depth, max_depth):
     gt = sample["gt_depth"]
     if args.gt_type == "NYU" and gt.ndim == 3:
         gt = gt[0]
     mask = sample["mask"] if args.gt_type == "KITTI" else (gt > min_depth) & (gt < max_depth)
     return gt, mask
+
+
+def prefetched(source, n, readers, ahead):
+    """source[0], source[1], ... in order, read by `readers` threads up to `ahead` items in front of the consumer."""
+    import collections
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=readers) as pool:
+        pending = collections.deque()
+        nxt = 0
+        for _ in range(n):
+            while nxt < n and len(pending) < ahead:
+                pending.append(pool.submit(source.__getitem__, nxt))
+                nxt += 1
+            yield pending.popleft().result()
 
 
 class DeviceEvaluator(object):
@@ -110,6 +136,10 @@ class DeviceEvaluator(object):
         self.mean_d = torch.tensor(mean, dtype=torch.float32, device=self.device)
         self.std_d = torch.tensor(std, dtype=torch.float32, device=self.device)
         self.ws = {}
+        self.image_ops = None                 # --device-resize: the frames are resized by dn_imresize_u8 (inference.ImageOps)
+        if getattr(args, "device_resize", False) and args.gt_type == "KITTI" and not args.no_resize:
+            from .inference import ImageOps
+            self.image_ops = ImageOps(self.device)
         self.scales = None                    # the scale each image of the last batch was given
 
     def _buf(self, name, numel, dtype):
@@ -170,7 +200,10 @@ class DeviceEvaluator(object):
     @torch.no_grad()
     def evaluate(self, samples):
         B = len(samples)
-        img = self._normalised([prepare_frame(self.args, s) for s in samples])
+        if self.image_ops is not None:
+            _, img = self.image_ops.imresize([raw_frame(s) for s in samples], network_size(self.args), list(self.mean_h), list(self.std_h))
+        else:
+            img = self._normalised([prepare_frame(self.args, s) for s in samples])
         gts, masks = zip(*(sample_ground_truth(self.args, s, self.lo, self.hi) for s in samples))
         hw, off, npix, total = ragged_layout([g.shape for g in gts])
         d_gt = self._upload("gt", pack_ragged(gts, np.float32, off, total))

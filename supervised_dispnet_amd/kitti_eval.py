@@ -174,8 +174,8 @@ class KittiTestFramework(object):
     """test_framework_KITTI (:11-30) for a list of 'date/scene/image_0X/data/index.png' entries (no pose displacements:
     the PoseNet-scaled evaluation is outside this path)."""
 
-    def __init__(self, root, test_files, min_depth=1e-3, max_depth=80):
-        self.root, self.min_depth, self.max_depth = root, min_depth, max_depth
+    def __init__(self, root, test_files, min_depth=1e-3, max_depth=80, keep_u8=False):
+        self.root, self.min_depth, self.max_depth, self.keep_u8 = root, min_depth, max_depth, keep_u8
         self.items = []
         for sample in test_files:
             img = os.path.join(root, sample)
@@ -191,7 +191,10 @@ class KittiTestFramework(object):
         img, calib, vel, cam = self.items[i]
         tgt = load_as_float(img)
         depth = generate_depth_map(calib, vel, tgt.shape[:2], cam)
-        return {"tgt": tgt, "path": img, "gt_depth": depth, "mask": generate_mask(depth, self.min_depth, self.max_depth)}
+        sample = {"tgt": tgt, "path": img, "gt_depth": depth, "mask": generate_mask(depth, self.min_depth, self.max_depth)}
+        if self.keep_u8:                          # eval_disp.py --device-resize uploads the bytes (exact: the file holds uint8)
+            sample["tgt_u8"] = tgt.astype(np.uint8)
+        return sample
 
     def __len__(self):
         return len(self.items)
