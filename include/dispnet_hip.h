@@ -635,6 +635,9 @@ int dn_eval_errors(const float* gt, const float* pred, const uint8_t* mask, cons
  * dn_contrast_u8 = PIL.ImageEnhance.Contrast(im).enhance(factor) on uint8[B][h][w][3]: L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16,
  * m = int(sum(L) / (h * w) + 0.5) (integer sum, one fp64 division), out = uint8(clip(fp32(m) + factor * (fp32(p) - fp32(m)), 0, 255)).
  * sum_ws = uint64[B][DN_IMAGE_CHUNKS] workspace; src != dst.
+ * dn_resize_u8 = PIL's Image.fromarray(frame).resize((w, h), Image.BILINEAR): dn_imresize_u8's two passes on the same tables WITHOUT the
+ * byte-scale, which is what scipy.misc.imresize does to a frame that is uint8 already (data/kitti_raw_loader.py:224).  Same ragged
+ * layout, tables and tap bound; the only output is out_u8 = uint8[B][h][w][3]; no workspace.
  * ------------------------------------------------------------------------------------------------------------ */
 #define DN_IMAGE_CHUNKS 64
 #define DN_IMRESIZE_MAX_TAPS 32
@@ -644,6 +647,26 @@ int dn_imresize_u8(const uint8_t* frames, const int32_t* hw, const int64_t* off,
 int dn_colorize_u8(const float* x, int32_t B, int32_t h, int32_t w, int32_t r0, int32_t r1, int32_t c0, int32_t c1, int32_t reciprocal,
                    float max_value, const uint8_t* table, float* max_ws, uint8_t* out, dn_stream_t stream);
 int dn_contrast_u8(const uint8_t* src, int32_t B, int32_t h, int32_t w, float factor, uint64_t* sum_ws, uint8_t* dst, dn_stream_t stream);
+int dn_resize_u8(const uint8_t* frames, const int32_t* hw, const int64_t* off, int32_t B, int32_t h, int32_t w, const int32_t* tabs,
+                 const int32_t* tab_idx, int32_t max_taps, uint8_t* out_u8, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Velodyne clouds -> sparse depth maps (reference data/kitti_raw_loader.py:243-300), a batch per call.
+ * points = fp32[total_points][4], the .bin files back to back as they are (column 3 is ignored and taken as 1.0; 16-byte aligned);
+ * pt_off = int64[B + 1] on the device, frame b owns points [pt_off[b], pt_off[b + 1]); M = fp64[B][12] on the device, the frame's 3 x 4
+ * P_velo2im (formed on the host); out = fp32[B][h][w], w >= 2.  A point with !(x >= 0) is dropped; per row i of M, in fp64 without
+ * contraction, p_i = ((M[i][0] * x + M[i][1] * y) + M[i][2] * z) + M[i][3]; u = p_0 / p_2, v = p_1 / p_2; col = rint(u) - 1,
+ * row = rint(v) - 1 (half to even); the point is kept iff col >= 0, row >= 0, col < lim_w, row < lim_h (NaN and inf fail); depth = p_2.
+ * 0 < lim_h <= h and 0 < lim_w <= w (the reference tests against img_height / ratio, the map has img_height // ratio rows).
+ * Every hit pixel takes the depth of the point with the largest index on it; every key row * (w - 1) + col - 1 (the reference's sub2ind:
+ * pixels (r, 0) and (r - 1, w - 1) share one) hit by more than one point then writes the minimum depth of its group at the pixel of the
+ * group's lowest-index point; negative values become 0; one fp64 -> fp32 rounding at the store.  Integer atomics only: the result does
+ * not depend on scheduling.  workspace: dn_velo_depth_workspace_bytes(B, h, w, total_points) bytes (0 for a bad shape), 8-byte aligned,
+ * contents irrelevant.  B <= 65535, total_points < 2^31 - 1.
+ * ------------------------------------------------------------------------------------------------------------ */
+size_t dn_velo_depth_workspace_bytes(int32_t B, int32_t h, int32_t w, int64_t total_points);
+int dn_velo_depth(const float* points, const int64_t* pt_off, int64_t total_points, const double* M, int32_t B, int32_t h, int32_t w,
+                  double lim_h, double lim_w, void* workspace, size_t workspace_bytes, float* out, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Attainable-peak probes (SURVEY.md section 8d "Peaks"; used by bench.py only): a float4 streaming copy of n floats

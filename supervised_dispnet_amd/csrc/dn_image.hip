@@ -6,6 +6,8 @@
 //                    coefficients the host hands over --, then optionally (x / 255 - mean) / std into the NCHW batch.  One block per
 //                    8 x 64 output tile: the horizontal pass covers the source rows the tile's vertical taps read and writes bytes into
 //                    LDS, the vertical pass reads LDS.  A frame that already is h x w passes through untouched.
+//   dn_resize_u8     the same two passes without the byte-scale: PIL's Image.resize((w, h), BILINEAR), which is what imresize does to a
+//                    frame that is uint8 already (kitti_raw_loader.py:224).
 //   dn_colorize_u8   utils.tensor2array of the reference (:45-76) times 255: crop, [1 / x], max, byte-scale, colour table or grey.
 //   dn_contrast_u8   PIL.ImageEnhance.Contrast(im).enhance(f): blend with the rounded mean of the image's luma.
 // The per-image reductions (min / max, max, luma sum) are two launches: DN_IMAGE_CHUNKS partials per image written by a first kernel and
@@ -94,8 +96,8 @@ __global__ void __launch_bounds__(kImgThreads) imresize_u8_kernel(const uint8_t*
   const uint8_t* f = frames + off[b];
 
   // the frame's byte-scale as a table: uint8(clip(fp32((fp32(a) - cmin) * fp32(255.0 / (cmax - cmin))) + 0.5f, 0, 255)); identity when
-  // the frame is passed through
-  if (!(hskip && vskip)) {
+  // the frame is passed through, and for dn_resize_u8 (minmax == nullptr: no stretch)
+  if (minmax != nullptr && !(hskip && vskip)) {
     if (tid < DN_IMAGE_CHUNKS * 2) smm[tid >> 1][tid & 1] = minmax[b * DN_IMAGE_CHUNKS * 2 + tid];
     __syncthreads();
     int cmin = 255, cmax = 0;
@@ -320,6 +322,20 @@ int dn_imresize_u8(const uint8_t* frames, const int32_t* hw, const int64_t* off,
   const float* sd = out_f32 ? std_host : one;
   DN_LAUNCH(imresize_u8_kernel, grid, dim3(kImgThreads), 0, s, frames, (const int*)hw, (const long long*)off, (const int*)tabs,
             (const int*)tab_idx, (const int*)minmax, (int)h, (int)w, out_u8, out_f32, m[0], m[1], m[2], sd[0], sd[1], sd[2]);
+  return check_launch("imresize_u8_kernel");
+}
+
+int dn_resize_u8(const uint8_t* frames, const int32_t* hw, const int64_t* off, int32_t B, int32_t h, int32_t w, const int32_t* tabs,
+                 const int32_t* tab_idx, int32_t max_taps, uint8_t* out_u8, dn_stream_t stream) {
+  DN_REQUIRE(frames && hw && off && tabs && tab_idx && out_u8 && B > 0 && B <= 65535 && h > 0 && w > 0, DN_ERR_BAD_ARG,
+             "dn_resize_u8: bad argument");
+  DN_REQUIRE(max_taps >= 0 && max_taps <= kRMaxTaps, DN_ERR_BAD_ARG,
+             "dn_resize_u8: %d taps per output exceed the bound of %d (a frame shrunk more than %d times along an axis)", (int)max_taps,
+             kRMaxTaps, (kRMaxTaps - 1) / 2);
+  dim3 grid((unsigned)((w + kRTileW - 1) / kRTileW), (unsigned)((h + kRTileH - 1) / kRTileH), (unsigned)B);
+  DN_REQUIRE(grid.y <= 65535, DN_ERR_UNSUPPORTED, "dn_resize_u8: h = %d is too large", (int)h);
+  DN_LAUNCH(imresize_u8_kernel, grid, dim3(kImgThreads), 0, as_stream(stream), frames, (const int*)hw, (const long long*)off,
+            (const int*)tabs, (const int*)tab_idx, (const int*)nullptr, (int)h, (int)w, out_u8, (float*)nullptr, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f);
   return check_launch("imresize_u8_kernel");
 }
 

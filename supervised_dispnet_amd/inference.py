@@ -85,7 +85,7 @@ class ImageOps(object):
         self.ws = {}
         self.tables, self.table_pos, self.pool = [], {}, None
 
-    def _stream(self):
+    def stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _buf(self, name, numel, dtype):
@@ -112,8 +112,8 @@ class ImageOps(object):
             self.pool = None
         return pos
 
-    def imresize(self, frames, size, mean=None, std=None, want_u8=False):
-        """[H_b x W_b x 3 uint8 arrays] -> (uint8 [B, h, w, 3] or None, normalised fp32 [B, 3, h, w] or None when mean is None)."""
+    def pack(self, frames, size):
+        """The ragged batch both resizes take: -> (B, h, w, packed bytes, hw, off, tab_idx, largest tap count), all on the host."""
         h, w = int(size[0]), int(size[1])
         B = len(frames)
         frames = [check_frame(f, "frame %d" % i) for i, f in enumerate(frames)]
@@ -129,6 +129,11 @@ class ImageOps(object):
         idx = np.array([self._table(W, w) + self._table(H, h) for H, W in hw], dtype=np.int32)
         if self.pool is None:
             self.pool = torch.from_numpy(np.concatenate([t.reshape(-1) for t in self.tables] or [np.zeros(1, np.int32)])).to(self.device)
+        return B, h, w, flat, hw, off, idx, int(idx[:, (1, 3)].max())
+
+    def imresize(self, frames, size, mean=None, std=None, want_u8=False):
+        """[H_b x W_b x 3 uint8 arrays] -> (uint8 [B, h, w, 3] or None, normalised fp32 [B, 3, h, w] or None when mean is None)."""
+        B, h, w, flat, hw, off, idx, taps = self.pack(frames, size)
         d_flat, d_hw, d_off, d_idx = (self._upload(n, a) for n, a in (("frames", flat), ("hw", hw), ("off", off), ("tab_idx", idx)))
         minmax = self._buf("minmax", B * IMAGE_CHUNKS * 2, torch.int32)
         u8 = torch.empty((B, h, w, 3), dtype=torch.uint8, device=self.device) if want_u8 else None
@@ -136,9 +141,27 @@ class ImageOps(object):
         mean_h = (ctypes.c_float * 3)(*mean) if mean is not None else None
         std_h = (ctypes.c_float * 3)(*std) if mean is not None else None
         _lib.call("dn_imresize_u8", d_flat.data_ptr(), d_hw.data_ptr(), d_off.data_ptr(), B, h, w, self.pool.data_ptr(), d_idx.data_ptr(),
-                  int(idx[:, (1, 3)].max()), minmax.data_ptr(), u8.data_ptr() if want_u8 else None, mean_h, std_h,
-                  f32.data_ptr() if f32 is not None else None, self._stream())
+                  taps, minmax.data_ptr(), u8.data_ptr() if want_u8 else None, mean_h, std_h,
+                  f32.data_ptr() if f32 is not None else None, self.stream())
         return u8, f32
+
+    def workspace(self, name, nbytes):
+        """A named uint8 device buffer of at least nbytes that is reused between calls (for callers that pack their own transfers)."""
+        return self._buf(name, nbytes, torch.uint8)
+
+    def resize_packed(self, B, h, w, flat, hw, off, idx, taps, out):
+        """dn_resize_u8 on a batch pack() made and the caller has uploaded: flat / hw / off / idx / out are device addresses (out: uint8
+        [B, h, w, 3]).  The one call site of the entry point."""
+        _lib.call("dn_resize_u8", flat, hw, off, B, h, w, self.pool.data_ptr(), idx, taps, out, self.stream())
+
+    def resize(self, frames, size):
+        """PIL's Image.fromarray(f).resize((w, h), Image.BILINEAR) of [H_b x W_b x 3 uint8 arrays] -> uint8 [B, h, w, 3] on the device
+        (dn_resize_u8: imresize without the byte-scale, what scipy.misc.imresize does to a uint8 frame)."""
+        B, h, w, flat, hw, off, idx, taps = self.pack(frames, size)
+        d_flat, d_hw, d_off, d_idx = (self._upload(n, a) for n, a in (("frames", flat), ("hw", hw), ("off", off), ("tab_idx", idx)))
+        u8 = torch.empty((B, h, w, 3), dtype=torch.uint8, device=self.device)
+        self.resize_packed(B, h, w, d_flat.data_ptr(), d_hw.data_ptr(), d_off.data_ptr(), d_idx.data_ptr(), taps, u8.data_ptr())
+        return u8
 
     def colorize(self, maps, rect=None, max_value=None, table=None, reciprocal=False):
         """255 * tensor2array(maps[b, r0:r1, c0:c1], max_value, table=table) as uint8 [B, r1-r0, c1-c0, 3] on the device.  maps: fp32
@@ -154,7 +177,7 @@ class ImageOps(object):
         ws = self._buf("max", B * IMAGE_CHUNKS, torch.float32)
         _lib.call("dn_colorize_u8", maps.data_ptr(), B, h, w, r0, r1, c0, c1, 1 if reciprocal else 0,
                   -1.0 if max_value is None else float(max_value), d_table.data_ptr() if d_table is not None else None, ws.data_ptr(),
-                  out.data_ptr(), self._stream())
+                  out.data_ptr(), self.stream())
         return out
 
     def contrast(self, images, factor):
@@ -163,7 +186,7 @@ class ImageOps(object):
         B, h, w, _ = images.shape
         out = torch.empty_like(images)
         ws = self._buf("lumasum", B * IMAGE_CHUNKS, torch.int64)
-        _lib.call("dn_contrast_u8", images.data_ptr(), B, h, w, float(factor), ws.data_ptr(), out.data_ptr(), self._stream())
+        _lib.call("dn_contrast_u8", images.data_ptr(), B, h, w, float(factor), ws.data_ptr(), out.data_ptr(), self.stream())
         return out
 
 
