@@ -357,6 +357,10 @@ struct SsimLocal {
 };
 
 __device__ __forceinline__ SsimLocal ssim_stats(const float* X, const float* Y, int H, int W, int y, int x) {
+  // No FMA contraction here: SSIM(x, x) must be exactly 1, i.e. n == d bit for bit when Y == X.  That holds when E[xy] - mx*my and
+  // E[xx] - mx*mx (and 2*mx*my, mx*mx + my*my) round alike; a compiler that fuses one of a pair and not the other breaks it by an ulp
+  // of E[xx], which the cancellation against mx*mx turns into 1e-7 of the output.
+#pragma clang fp contract(off)
   float sx = 0.f, sy = 0.f, sxx = 0.f, syy = 0.f, sxy = 0.f;
 #pragma unroll
   for (int dy = -1; dy <= 1; ++dy)

@@ -5,6 +5,8 @@ oracle on larger, ragged shapes.  pytest -m gpu.
 Stated tolerances: scalar losses rtol 1e-5 (2e-5 where an exp/log chain is involved); per-pixel gradients rtol 1e-4 with an
 absolute floor relative to max|ref|; warped images atol 2e-5 (a bilinear gather of fp32 coordinates: coordinate round-off
 of ~1e-6 px times image gradient); pose gradients rtol 1e-3 (sums over all pixels); integer outputs exact.
+The fp64 comparison of the warp / photometric / SSIM / smoothness kernels, on inputs that fire their out-of-range, clamp and grid-stride
+branches and with a measured tolerance, is tests/test_gpu_geom_fp64.py (cases and checker: tests/geom_audit.py).
 """
 import numpy as np
 import pytest
