@@ -1462,7 +1462,6 @@ __global__ void __launch_bounds__(256) stem_conv_kernel(const IgemmParams p) {
 }
 
 static bool stem_eligible(const dn_conv_desc* d, const IgemmParams& p) {
-  if (false) return false;
   if (d->kind != DN_CONV_FWD || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || d->pad_mode != 0 || d->dilation > 1) return false;
   if (p.n_in != 1 || p.n_out != 1 || p.Ntot != 64 || p.nphases != 1) return false;
   const KOperand& o = p.in[0];
@@ -2176,7 +2175,7 @@ static int launch_conv(const IgemmParams& p, hipStream_t stream) {
   return p.allvec ? launch_conv_v<BM, BN, WM, WN, true>(p, stream) : launch_conv_v<BM, BN, WM, WN, false>(p, stream);
 }
 
-// The tiled kernels: every layer no other family of run_conv takes.  Picks the tile shape.
+// The tiled kernels: every layer no other row of kConvFamilies takes.  Picks the tile shape.
 static int launch_tiled_conv(const IgemmParams& p, hipStream_t s) {
   // Few row tiles (the 4x13 / 8x26 decoder levels at b32: 13-52 tiles of 128 rows) leave most of the 256 CUs without a block;
   // 64-row tiles double the block count at the same per-wave MFMA density along N.  Not with batch statistics: the
@@ -2201,6 +2200,42 @@ static int launch_tiled_conv(const IgemmParams& p, hipStream_t s) {
   }
 }
 
+// The forward / input-gradient / conv-transpose kernel families in priority order; the tiled kernels, last, take every plan.  conv_route
+// returns the first eligible row: run_conv launches it, the weight re-lay follows its layout, and the host queries of dn_plan.hip -- on
+// whose answers the engine allocates recip_out, skips dn_bn_finalize and takes sums for finished -- read its columns.  Which template
+// instance a row runs (tile shape, Winograd variant) is its launch's business.  A new family adds one row here.
+template <auto Launch> static int plan_only(const dn_conv_desc*, IgemmParams& p, hipStream_t s) { return Launch(p, s); }
+template <auto Launch> static int with_desc(const dn_conv_desc* d, IgemmParams& p, hipStream_t s) { return Launch(d, p, s); }
+static bool heads_off() { return knobs().no_direct; }
+// Split-K bytes of every row but Winograd's: the three-piece tiled kernel's.  Only the tiled row splits; for the others it is an upper
+// bound that no launch of the row uses, kept because that is what callers have always been told.
+constexpr auto x3_upper = conv_x3_splitk_workspace_upper_bytes;
+static const ConvFamily kConvFamilies[] = {
+    {"head_fwd", head_fwd_eligible, heads_off, plan_only<launch_head_fwd>, nullptr, x3_upper, head_fwd_fuses_reciprocal},
+    {"head_dgrad", head_dgrad_eligible, heads_off, plan_only<launch_head_dgrad>, nullptr, x3_upper},
+    {"winograd", wino_eligible, nullptr, plan_only<launch_wino_conv>, wino_layout,
+     [](const IgemmParams& p) { return wino_layout(p) == 3 ? wino_splitk_workspace_bytes(p) : (size_t)0; }, nullptr,
+     [](const dn_conv_desc* d) {
+       const dn_result& r = d->out[0];
+       return d->kind == DN_CONV_DGRAD && d->n_out == 1 && !r.accumulate && (r.C & 3) == 0 && r.stride_w == r.C &&
+              r.stride_h == (int64_t)d->OW * r.C && r.stride_n == (int64_t)d->OH * d->OW * r.C && d->bias == nullptr && d->act == DN_ACT_NONE;
+     },
+     [](IgemmParams& p) { wino_prepare(p); return wino_folds_bn_finalize(p); }, [](IgemmParams& p) { wino_prepare(p); return wino_folds_bn_sums(p); }},
+    {"stem3", stem3_conv_eligible, nullptr, plan_only<launch_stem3_conv>, nullptr, x3_upper},
+    {"stemk", stemk_conv_eligible, nullptr, with_desc<launch_stemk_conv>, nullptr, x3_upper},
+    {"stem", stem_eligible, nullptr, plan_only<launch_stem>, nullptr, x3_upper},
+    {"lds3", lds3_conv_eligible, nullptr, with_desc<launch_lds3_conv>, nullptr, x3_upper},
+    {"lds3k", lds3k_conv_eligible, nullptr, with_desc<launch_lds3k_conv>, nullptr, x3_upper},
+    {"thin", thin_conv_eligible, nullptr, plan_only<launch_thin_conv>, nullptr, x3_upper},
+    {"tiled", [](const dn_conv_desc*, const IgemmParams&) { return true; }, nullptr, plan_only<launch_tiled_conv>, nullptr, x3_upper},
+};
+
+const ConvFamily* conv_route(const dn_conv_desc* d, const IgemmParams& p) {
+  const ConvFamily* f = kConvFamilies;
+  while (!f->eligible(d, p) || (f->switched_off && f->switched_off())) ++f;
+  return f;
+}
+
 static int run_conv(const dn_conv_desc* d, int expect_kind, dn_stream_t stream) {
   DN_REQUIRE(d != nullptr && d->kind == expect_kind, DN_ERR_BAD_ARG, "descriptor kind mismatch (want %d)", expect_kind);
   IgemmParams p;
@@ -2213,22 +2248,7 @@ static int run_conv(const dn_conv_desc* d, int expect_kind, dn_stream_t stream) 
     DN_REQUIRE(o.stride_h == (int64_t)d->OW * o.stride_w && o.stride_n == (int64_t)d->OH * o.stride_h, DN_ERR_UNSUPPORTED,
                "result %d must be pixel-dense (NHWC with a channel stride)", i);
   }
-  hipStream_t s = as_stream(stream);
-  if (!knobs().no_direct) {
-    if (head_fwd_eligible(d, p)) return launch_head_fwd(p, s);
-    if (head_dgrad_eligible(d, p)) return launch_head_dgrad(p, s);
-  }
-  if (const int wl = wino_layout(d, p)) {
-    p.compute = wl == 2 ? DN_COMPUTE_BF16 : (wl == 3 ? DN_COMPUTE_F32X3 : DN_COMPUTE_F32);
-    return launch_wino_conv(p, s);
-  }
-  if (stem3_conv_eligible(d, p)) return launch_stem3_conv(p, s);
-  if (stemk_conv_eligible(d, p)) return launch_stemk_conv(d, p, s);
-  if (stem_eligible(d, p)) return launch_stem(p, s);
-  if (lds3_conv_eligible(d, p)) return launch_lds3_conv(d, p, s);
-  if (lds3k_conv_eligible(d, p)) return launch_lds3k_conv(d, p, s);
-  if (thin_conv_eligible(d, p)) return launch_thin_conv(p, s);
-  return launch_tiled_conv(p, s);
+  return conv_route(d, p)->launch(d, p, as_stream(stream));
 }
 
 template <int BNW, int WNn, int WKk, bool ALLVEC>
@@ -2464,12 +2484,12 @@ int dn_pack_entry_fill(const dn_conv_desc* d, const float* w, float* w_packed, v
   if (rc != DN_OK) return rc;
   e->w = w;
   e->wp = w_packed;
-  if (const int wl = wino_layout(d, e->p)) {
-    e->wino = wl;
+  const ConvFamily* f = conv_route(d, e->p);
+  e->wino = f->weight_layout ? f->weight_layout(e->p) : 0;
+  if (e->wino) {
     e->total = wino_packed_elems(e->p);
     e->NS = ((e->p.Ntot + 63) / 64 * 64) / 32;
   } else {
-    e->wino = 0;
     e->total = direct_packed_elems(e->p);
     e->NS = 0;
   }
@@ -2502,7 +2522,8 @@ int dn_conv_pack_weights(const dn_conv_desc* d, const float* w, float* w_packed,
   int rc = build_plan(d, false, &p);
   if (rc != DN_OK) return rc;
   DN_REQUIRE(w != nullptr && w_packed != nullptr, DN_ERR_BAD_ARG, "null weight pointer");
-  if (const int wl = wino_layout(d, p))
+  const ConvFamily* f = conv_route(d, p);
+  if (const int wl = f->weight_layout ? f->weight_layout(p) : 0)
     return wl == 1 ? launch_wino_pack(p, w, w_packed, as_stream(stream)) : launch_wino_pack16(p, w, w_packed, wl == 3 ? 3 : 1, as_stream(stream));
   const long long total = direct_packed_elems(p);
   if (total == 0) return DN_OK;

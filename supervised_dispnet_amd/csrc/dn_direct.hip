@@ -376,8 +376,11 @@ static bool head2_geometry(const IgemmParams& p, int C) {
   return true;
 }
 
+// the 3x3 form of the forward head (head_fwd2_kernel), the one that can write the reciprocal as well
+static bool head_fwd2_form(const IgemmParams& p) { return head2_geometry(p, p.in[0].C) && p.GH == p.IH && p.GW == p.IW; }
+
 int launch_head_fwd(const IgemmParams& p, hipStream_t stream) {
-  if (head2_geometry(p, p.in[0].C) && p.GH == p.IH && p.GW == p.IW) {
+  if (head_fwd2_form(p)) {
     const int LGc = log2_exact(p.in[0].C / 16);
     const int big = p.N * ((p.GW + 63) / 64) * ((p.GH + 7) / 8);
     if (big >= 1024) {
@@ -401,9 +404,7 @@ int launch_head_fwd(const IgemmParams& p, hipStream_t stream) {
   return check_launch("head_fwd_kernel");
 }
 
-bool head_fwd_fuses_reciprocal(const dn_conv_desc* d, const IgemmParams& p) {
-  return !knobs().no_direct && head_fwd_eligible(d, p) && head2_geometry(p, p.in[0].C) && p.GH == p.IH && p.GW == p.IW && !p.out[0].accumulate;
-}
+bool head_fwd_fuses_reciprocal(const IgemmParams& p) { return head_fwd2_form(p) && !p.out[0].accumulate; }
 
 bool head_dgrad_eligible(const dn_conv_desc* d, const IgemmParams& p) {
   return d->kind == DN_CONV_DGRAD && p.n_in == 1 && p.in[0].C == 1 && p.in[0].up == 0 && p.in[0].scale == nullptr && p.n_out == 1 &&

@@ -223,15 +223,31 @@ int launch_wino_pack_many(const PackEntry* tab_dev, int first, int n, hipStream_
 int launch_wino_pack16_many(const PackEntry* tab_dev, int first, int n, int pieces, hipStream_t stream);
 int launch_wino_pack16(const IgemmParams& p, const float* w, float* wp, int pieces, hipStream_t stream);
 long long wino_packed_floats(const IgemmParams& p, int layout);
-int wino_layout(const dn_conv_desc* d, const IgemmParams& p);
+int wino_layout(const IgemmParams& p);     // of a layer the Winograd family takes: 1 fp32, 2 bf16, 3 three bf16 pieces
 
-// ---- kernel families.  Which one a conv call runs is decided in dn_conv.hip and nowhere else: forward / input gradient by the chain of
-// *_eligible calls in run_conv (ending in launch_tiled_conv), the weight gradient by the rows of kWgradFamilies (sizing and launch
-// read the same rows), then the leading-pieces split, the tap windows and the tiled kernel.
+// ---- kernel families.  Which one a conv call runs is decided in dn_conv.hip and nowhere else, by two tables of one row per family in
+// priority order.  Forward / input gradient / conv-transpose: kConvFamilies, whose first eligible row (conv_route) the launch, the weight
+// re-lay and the host queries of dn_plan.hip all read.  Weight gradient: kWgradFamilies (sizing and launch read the same rows), then the
+// leading-pieces split, the tap windows and the tiled kernel.
+struct ConvFamily {
+  const char* name;
+  bool (*eligible)(const dn_conv_desc* d, const IgemmParams& p);
+  bool (*switched_off)();                                  // a switch that takes the row out, or nullptr
+  int (*launch)(const dn_conv_desc* d, IgemmParams& p, hipStream_t s);
+  // what the host queries answer for a call the row takes, on the caller's own plan (a column may prepare it as the launch would)
+  int (*weight_layout)(const IgemmParams& p);              // nullptr: 0, the implicit-GEMM layout of direct_packed_elems()
+  size_t (*splitk_workspace_bytes)(const IgemmParams& p);  // most bytes of dn_conv_desc.splitk_ws a launch of the row uses
+  bool (*fuses_reciprocal)(const IgemmParams& p);          // writes recip_out; nullptr (here and below): never
+  bool (*takes_bn_sums)(const dn_conv_desc* d);            // an input gradient that writes bnb_partial
+  bool (*folds_bn_finalize)(IgemmParams& p);               // finishes the BatchNorm statistics itself
+  bool (*folds_bn_sums)(IgemmParams& p);                   // of a call that takes_bn_sums: finishes those sums itself
+};
+const ConvFamily* conv_route(const dn_conv_desc* d, const IgemmParams& p);   // never null: the last row takes every plan
+
 // dn_direct.hip: matrix-core-free kernels for the one-channel disparity heads
 bool head_fwd_eligible(const dn_conv_desc* d, const IgemmParams& p);
 int launch_head_fwd(const IgemmParams& p, hipStream_t stream);
-bool head_fwd_fuses_reciprocal(const dn_conv_desc* d, const IgemmParams& p);
+bool head_fwd_fuses_reciprocal(const IgemmParams& p);   // of a layer head_fwd_eligible takes
 bool head_dgrad_eligible(const dn_conv_desc* d, const IgemmParams& p);
 int launch_head_dgrad(const IgemmParams& p, hipStream_t stream);
 bool head_wgrad_eligible(const dn_conv_desc* fwd, const IgemmParams& p);
@@ -243,6 +259,7 @@ bool wino_eligible(const dn_conv_desc* d, const IgemmParams& p);
 long long wino_packed_elems(const IgemmParams& p);
 int launch_wino_pack(const IgemmParams& p, const float* w, float* wp, hipStream_t stream);
 int launch_wino_conv(IgemmParams& p, hipStream_t stream);
+void wino_prepare(IgemmParams& p);                   // arithmetic and tile fields of a Winograd launch; the two below read them
 bool wino_folds_bn_finalize(const IgemmParams& p);   // the launch will finish the BatchNorm statistics / the BatchNorm-backward sums itself
 bool wino_folds_bn_sums(const IgemmParams& p);
 int wino_splitk_choice(const IgemmParams& p);

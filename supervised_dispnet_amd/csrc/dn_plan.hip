@@ -383,11 +383,17 @@ int build_plan(const dn_conv_desc* d, bool for_wgrad, IgemmParams* p) {
   return DN_OK;
 }
 
+// The conv host queries below answer from the row of kConvFamilies (dn_conv.hip) that the launch of the same descriptor takes.
+// Plans d into *p and returns that row, or nullptr for a descriptor the plan refuses.
+static const ConvFamily* plan_route(const dn_conv_desc* d, IgemmParams* p) {
+  return build_plan(d, false, p) == DN_OK ? conv_route(d, *p) : nullptr;
+}
+
 }  // namespace dn
 
 extern "C" {
 
-int dn_version(void) { return 20; }
+int dn_version(void) { return 21; }
 
 void dn_reload_knobs(void) {
   std::lock_guard<std::mutex> lock(dn::g_knobs_mu);
@@ -415,15 +421,15 @@ int dn_device_arch_ok(void) {
 
 int64_t dn_conv_packed_weight_elems(const dn_conv_desc* d) {
   dn::IgemmParams p;
-  if (dn::build_plan(d, false, &p) != DN_OK) return -1;
-  if (const int wl = dn::wino_layout(d, p)) return dn::wino_packed_floats(p, wl);
-  return dn::direct_packed_elems(p);
+  const dn::ConvFamily* f = dn::plan_route(d, &p);
+  if (f == nullptr) return -1;
+  return f->weight_layout ? dn::wino_packed_floats(p, f->weight_layout(p)) : dn::direct_packed_elems(p);
 }
 
 int32_t dn_conv_weight_layout(const dn_conv_desc* d) {
   dn::IgemmParams p;
-  if (dn::build_plan(d, false, &p) != DN_OK) return -1;
-  return dn::wino_layout(d, p);
+  const dn::ConvFamily* f = dn::plan_route(d, &p);
+  return f == nullptr ? -1 : (f->weight_layout ? f->weight_layout(p) : 0);
 }
 
 int32_t dn_conv_bn_partial_rows(const dn_conv_desc* d) {
@@ -434,43 +440,32 @@ int32_t dn_conv_bn_partial_rows(const dn_conv_desc* d) {
 
 int32_t dn_conv_fwd_fuses_reciprocal(const dn_conv_desc* d) {
   dn::IgemmParams p;
-  if (d == nullptr || d->kind != DN_CONV_FWD || dn::build_plan(d, false, &p) != DN_OK) return 0;
-  return dn::head_fwd_fuses_reciprocal(d, p) ? 1 : 0;
+  const dn::ConvFamily* f = dn::plan_route(d, &p);
+  return (f != nullptr && f->fuses_reciprocal && f->fuses_reciprocal(p)) ? 1 : 0;
 }
 
 int32_t dn_conv_dgrad_fuses_bn_sums(const dn_conv_desc* d) {
   dn::IgemmParams p;
-  if (d == nullptr || dn::build_plan(d, false, &p) != DN_OK) return -1;
-  if (d->kind != DN_CONV_DGRAD) return 0;
-  if (dn::wino_layout(d, p) == 0) return 0;
-  const dn_result& r = d->out[0];
-  const bool dense = d->n_out == 1 && !r.accumulate && (r.C & 3) == 0 && r.stride_w == r.C && r.stride_h == (int64_t)d->OW * r.C &&
-                     r.stride_n == (int64_t)d->OH * d->OW * r.C;
-  return (dense && d->bias == nullptr && d->act == DN_ACT_NONE) ? 1 : 0;
+  const dn::ConvFamily* f = dn::plan_route(d, &p);
+  return f == nullptr ? -1 : ((f->takes_bn_sums && f->takes_bn_sums(d)) ? 1 : 0);
 }
 
 int32_t dn_conv_fwd_folds_bn_finalize(const dn_conv_desc* d) {
   dn::IgemmParams p;
-  if (d == nullptr || dn::build_plan(d, false, &p) != DN_OK) return -1;
-  if (d->kind != DN_CONV_FWD || dn::wino_layout(d, p) == 0) return 0;
-  p.T = p.M / 4;
-  return dn::wino_folds_bn_finalize(p) ? 1 : 0;
+  const dn::ConvFamily* f = dn::plan_route(d, &p);
+  return f == nullptr ? -1 : ((f->folds_bn_finalize && f->folds_bn_finalize(p)) ? 1 : 0);
 }
 
 int32_t dn_conv_dgrad_folds_bn_sums(const dn_conv_desc* d) {
-  if (dn_conv_dgrad_fuses_bn_sums(d) != 1) return 0;
   dn::IgemmParams p;
-  if (dn::build_plan(d, false, &p) != DN_OK) return -1;
-  p.T = p.M / 4;
-  return dn::wino_folds_bn_sums(p) ? 1 : 0;
+  const dn::ConvFamily* f = dn::plan_route(d, &p);
+  return (f != nullptr && f->takes_bn_sums && f->takes_bn_sums(d) && f->folds_bn_sums(p)) ? 1 : 0;
 }
 
 int64_t dn_conv_splitk_workspace_bytes(const dn_conv_desc* d) {
   dn::IgemmParams p;
-  if (d == nullptr || dn::build_plan(d, false, &p) != DN_OK) return -1;
-  const int wl = dn::wino_layout(d, p);
-  if (wl == 3) return (int64_t)dn::wino_splitk_workspace_bytes(p);
-  return wl != 0 ? 0 : (int64_t)dn::conv_x3_splitk_workspace_upper_bytes(p);
+  const dn::ConvFamily* f = dn::plan_route(d, &p);
+  return f != nullptr ? (int64_t)f->splitk_workspace_bytes(p) : -1;
 }
 
 // Test/diagnostic hook (host only, no device work): dump the plan as int32s.
@@ -495,6 +490,13 @@ int dn_debug_conv_plan(const dn_conv_desc* d, int for_wgrad, int32_t* out, int c
     }
   }
   return n;
+}
+
+// Test/diagnostic hook (host only): the name of the kConvFamilies row the launch of d takes, "reject" for a descriptor the plan refuses.
+const char* dn_debug_conv_route(const dn_conv_desc* d) {
+  dn::IgemmParams p;
+  const dn::ConvFamily* f = dn::plan_route(d, &p);
+  return f != nullptr ? f->name : "reject";
 }
 
 }  // extern "C"

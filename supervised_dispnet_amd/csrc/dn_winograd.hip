@@ -40,9 +40,7 @@ namespace dn {
 bool wino_eligible(const dn_conv_desc* d, const IgemmParams& p) {
   if (knobs().no_winograd) return false;
   if (!(d->kind == DN_CONV_FWD || d->kind == DN_CONV_DGRAD)) return false;
-  // the one-channel disparity heads have their own kernels, dispatched before this one (dn_conv.hip::run_conv); the packed
-  // weight layout must follow the same decision (a head's input gradient has a 1-channel operand and would qualify below)
-  if (!knobs().no_direct && (head_fwd_eligible(d, p) || head_dgrad_eligible(d, p))) return false;
+  // (a one-channel head's input gradient has a 1-channel operand and qualifies below: the head rows stand before this one in kConvFamilies)
   if (d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || d->pad_mode != 0 || d->dilation > 1) return false;
   if (d->IH != d->OH || d->IW != d->OW || (d->OH & 1) || (d->OW & 1)) return false;
   if (p.nphases != 1 || p.ph[0].ntaps != 9) return false;
@@ -297,13 +295,11 @@ int launch_wino_pack16(const IgemmParams& p, const float* w, float* wp, int piec
   return check_launch("wino_pack16_kernel");
 }
 
-// 0: not a Winograd layer; 1: fp32 Winograd; 2: bf16-multiply Winograd (descriptor compute = DN_COMPUTE_BF16); 3: fp32 products from
+// Packed layout of a layer wino_eligible takes.  1: fp32 Winograd; 2: bf16-multiply Winograd (descriptor compute = DN_COMPUTE_BF16); 3: fp32 products from
 // three bf16 pieces per operand (DN_COMPUTE_F32X3) -- the last two on the default tile variant only
-int wino_layout(const dn_conv_desc* d, const IgemmParams& p) {
-  if (!wino_eligible(d, p)) return 0;
+int wino_layout(const IgemmParams& p) {
   if (knobs().wino_dbg != 0 && knobs().wino_dbg != 4 && knobs().wino_dbg < 16) return 1;
   if (p.compute == DN_COMPUTE_F32X3) return 3;          // (either tile height)
-  if (1 != 1) return 1;
   return p.compute == DN_COMPUTE_BF16 ? 2 : 1;
 }
 
@@ -1116,13 +1112,19 @@ static int launch_wino_variant(const IgemmParams& p, hipStream_t stream) {
   return check_launch("wino_conv_kernel");
 }
 
-int launch_wino_conv(IgemmParams& p, hipStream_t stream) {
+void wino_prepare(IgemmParams& p) {
+  const int wl = wino_layout(p);
+  p.compute = wl == 2 ? DN_COMPUTE_BF16 : (wl == 3 ? DN_COMPUTE_F32X3 : DN_COMPUTE_F32);
   p.Npad = wino_npad(p);
   p.T = p.M / 4;
   p.TH = p.OH / 2;
   p.TW = p.OW / 2;
   p.mTW = fastdiv_magic((unsigned)p.TW);
   p.mTH = fastdiv_magic((unsigned)p.TH);
+}
+
+int launch_wino_conv(IgemmParams& p, hipStream_t stream) {
+  wino_prepare(p);
   {   // tile order within an XCD (DN_WINO_NMAJOR: 0 cout slice fastest, 1 tile row fastest, 2/3: tile row fastest from 4 / 8 cout slices).
       // Three-piece kernels only: the bf16-rounded and fp32-instruction variants came out 0.2-0.6 % slower with it (profiles/r05_exp28)
     const int nm = knobs().wino_nmajor, nt = p.Npad / WBN;

@@ -16,16 +16,32 @@ family table was introduced:
     DISPNET_HIP_LIB=<that build's libdispnet_hip.so> python tests/test_conv_sizing.py --record
 
 and is only to be re-recorded, the same way, by a change that means to alter a size.  Equality is exact.
+
+Routes.  Which forward family (row of kConvFamilies in dn_conv.hip) takes a forward / input-gradient / conv-transpose call decides the
+launch, the packed weight layout and what the host queries promise the engine (a reciprocal written, statistics finished).
+tests/golden/conv_routes.json pins dn_debug_conv_route for the same descriptor list: {switch: {key: [forward route, input-gradient
+route]}} with the switch "default" (none set) or one of ROUTE_SWITCHES.  It was recorded against the library built from the commit
+BEFORE that table was introduced, which decided by a chain of if statements in run_conv; that build carried one addition,
+dn_debug_conv_route written as a literal copy of the chain with `return "name"` in place of each launch (and reported the ABI version
+of its day, which the recording run told the binding to expect):
+
+    DISPNET_HIP_LIB=<that build's libdispnet_hip.so> python tests/test_conv_sizing.py --record-routes
+
+Re-record only in a change that means to move a layer from one family to another.
 """
 import ctypes as C
 import json
 import pathlib
+import re
 import sys
 
 import pytest
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden" / "conv_sizing.json"
+ROUTE_GOLDEN = ROOT / "tests" / "golden" / "conv_routes.json"
+ROUTES = ("head_fwd", "head_dgrad", "winograd", "stem3", "stemk", "stem", "lds3", "lds3k", "thin", "tiled")    # the rows of kConvFamilies
+ROUTE_SWITCHES = ("DN_NO_WINOGRAD", "DN_NO_DIRECT", "DN_NO_LDS3", "DN_NO_THIN_CONV")
 BATCHES = (4, 32)
 
 
@@ -206,6 +222,11 @@ def measure(lib):
     return got
 
 
+def routes(lib):
+    """key -> [forward route, input-gradient route]"""
+    return {key: [lib.dn_debug_conv_route(C.byref(f)).decode(), lib.dn_debug_conv_route(C.byref(g)).decode()] for key, f, g in descriptors()}
+
+
 # ------------------------------------------------------------------------------------------------------------ the tests
 @pytest.fixture(scope="module")
 def lib():
@@ -241,11 +262,63 @@ def test_each_switchable_family_sizes_some_descriptor(lib, monkeypatch, switch):
     assert any(off[k] != base[k] for k in base), "%s changes no weight-gradient workspace of the list" % switch
 
 
+@pytest.fixture(params=("default",) + ROUTE_SWITCHES)
+def switch(request, lib, monkeypatch):
+    if request.param != "default":
+        monkeypatch.setenv(request.param, "1")
+    lib.dn_reload_knobs()
+    yield request.param
+    monkeypatch.undo()
+    lib.dn_reload_knobs()
+
+
+def test_the_route_list_is_the_family_table():
+    src = (ROOT / "supervised_dispnet_amd" / "csrc" / "dn_conv.hip").read_text()
+    table = src[src.index("kConvFamilies[] = {"):]
+    table = table[:table.index("\n};")]
+    assert tuple(re.findall(r'^    \{"(\w+)",', table, re.M)) == ROUTES
+
+
+def test_routes_match_the_recorded_values(lib, switch):
+    want = json.loads(ROUTE_GOLDEN.read_text())
+    assert sorted(want) == sorted(("default",) + ROUTE_SWITCHES)
+    got = routes(lib)
+    assert sorted(got) == sorted(want[switch]), "the descriptor list and the recorded list differ"
+    bad = {k: (got[k], want[switch][k]) for k in got if got[k] != want[switch][k]}
+    assert not bad, "%s: %d of %d descriptors route differently (got, recorded): %s" % (switch, len(bad), len(got), sorted(bad.items())[:8])
+    if switch == "default":
+        # a row the list does not reach would go unpinned (head_dgrad by input gradients only, the stems by forwards only)
+        assert {r for v in got.values() for r in v} == set(ROUTES)
+    else:
+        assert got != want["default"], "%s moves no descriptor of the list" % switch
+
+
+def test_queries_agree_with_the_route(lib, switch):
+    """What the engine acts on (the layout it packs, the reciprocal buffer it allocates, the BatchNorm-backward sums it leaves to the
+    input gradient) belongs to the family that will run."""
+    for key, f, g in descriptors():
+        for d in (f, g):
+            route = lib.dn_debug_conv_route(C.byref(d)).decode()
+            assert (lib.dn_conv_weight_layout(C.byref(d)) != 0) == (route == "winograd"), key
+            assert lib.dn_conv_fwd_fuses_reciprocal(C.byref(d)) != 1 or route == "head_fwd", key
+            assert lib.dn_conv_dgrad_fuses_bn_sums(C.byref(d)) != 1 or route == "winograd", key
+
+
 if __name__ == "__main__":
     sys.path.insert(0, str(ROOT))
     from supervised_dispnet_amd import _lib as _binding
+    if "--record-routes" in sys.argv:
+        import os
+        lib, recorded = _binding.load(), {}
+        for sw in ("default",) + ROUTE_SWITCHES:
+            os.environ.update({sw: "1"} if sw != "default" else {})
+            lib.dn_reload_knobs()
+            recorded[sw] = routes(lib)
+            os.environ.pop(sw, None)
+        ROUTE_GOLDEN.write_text(json.dumps(recorded, indent=0, sort_keys=True, separators=(",", ":")) + "\n")
+        sys.exit("recorded %d descriptors x %d switch settings from %s" % (len(recorded["default"]), len(recorded), _binding.LIB_PATH))
     if "--record" not in sys.argv:
-        sys.exit("usage: DISPNET_HIP_LIB=<reference build> python tests/test_conv_sizing.py --record")
+        sys.exit("usage: DISPNET_HIP_LIB=<reference build> python tests/test_conv_sizing.py --record | --record-routes")
     values = measure(_binding.load())
     GOLDEN.write_text(json.dumps(values, indent=0, sort_keys=True, separators=(",", ":")) + "\n")
     print("recorded %d descriptors from %s" % (len(values), _binding.LIB_PATH))

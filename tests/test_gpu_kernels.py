@@ -779,3 +779,93 @@ def test_winograd8_tail_split_of_the_last_partial_round(case):
         assert torch.equal(y2, ys) and torch.equal(y3, ys)
     finally:
         engine.SPLITK = prev
+
+
+# ---- one call per row of kConvFamilies (dn_conv.hip): the row dn_debug_conv_route names is the row that runs
+# (route, kind, compute, k, stride, pad, pieces (C, planar NCHW), cout, N, (H, W) of the forward input): the smallest shapes the host
+# query still routes to each row -- two 8 x 32 stem3 tiles, 208 Winograd tiles (the floor is 192), 192 ragged 4 x 32 lds3k tiles and
+# 128 stemk tiles of 16 x 32 results (their floors), the others a handful of pixels
+_X3, _F32 = _lib.COMPUTE_F32X3, _lib.COMPUTE_F32
+ROUTE_CASES = [
+    ("head_fwd", _lib.CONV_FWD, _X3, 3, 1, 1, [(16, False)], 1, 1, (4, 8)),
+    ("head_dgrad", _lib.CONV_DGRAD, _X3, 3, 1, 1, [(16, False)], 1, 1, (4, 8)),
+    ("winograd", _lib.CONV_FWD, _X3, 3, 1, 1, [(64, False)], 64, 1, (16, 52)),
+    ("stem3", _lib.CONV_FWD, _X3, 3, 1, 1, [(3, True)], 64, 1, (16, 32)),
+    ("stemk", _lib.CONV_FWD, _X3, 7, 2, 3, [(3, True)], 64, 4, (128, 512)),
+    ("stem", _lib.CONV_FWD, _F32, 3, 1, 1, [(3, True)], 64, 1, (16, 32)),
+    ("lds3", _lib.CONVT_FWD, _X3, 4, 2, 1, [(32, False)], 16, 1, (2, 4)),
+    ("lds3k", _lib.CONV_FWD, _X3, 3, 1, 1, [(32, False), (64, False), (1, False)], 32, 1, (94, 226)),
+    ("thin", _lib.CONVT_FWD, _F32, 4, 2, 1, [(32, False)], 16, 1, (2, 4)),
+    ("tiled", _lib.CONV_FWD, _X3, 3, 2, 1, [(32, False)], 48, 1, (4, 8)),
+]
+ROUTE_KERNELS = {"head_fwd": "dn::head_fwd", "head_dgrad": "dn::head_dgrad", "winograd": "dn::wino_conv", "stem3": "dn::stem3_conv_kernel",
+                 "stemk": "dn::stemk_conv_kernel", "stem": "dn::stem_conv_kernel", "lds3": "dn::lds3_conv_kernel", "lds3k": "dn::lds3k_conv_kernel",
+                 "thin": "dn::thin_conv_kernel", "tiled": "dn::igemm_conv"}
+
+
+@pytest.mark.parametrize("case", ROUTE_CASES, ids=[c[0] for c in ROUTE_CASES])
+def test_each_conv_family_row_runs_what_the_route_names(case):
+    """A descriptor on real tensors, its weights packed by dn_conv_pack_weights: dn_debug_conv_route names the row, the launch runs a
+    kernel of that row, and the result is F.conv2d / F.conv_transpose2d of the same inputs in fp64 to the suite's relative L2 of an fp32
+    result (conv_audit.REL_L2).  The forward head also writes the reciprocal it promises (within 1 ulp of 1 / its own result)."""
+    import ctypes as C
+    from conv_audit import REL_L2
+    route, kind, compute, k, s, p, pieces, cout, N, (H, W) = case
+    lib = _lib.load()
+    transposed = kind == _lib.CONVT_FWD
+    cin = sum(c for c, _ in pieces)
+    OH, OW = ((H - 1) * s - 2 * p + k, (W - 1) * s - 2 * p + k) if transposed else ((H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1)
+    lo = 0.5 if route == "head_fwd" else -1.0          # a positive disparity, away from zero: its reciprocal is checked
+    w = rnd(*((cin, cout) if transposed else (cout, cin)), k, k, lo=lo / 2, seed=1)
+    d = _lib.ConvDesc()
+    d.kind, d.N, d.R, d.S, d.stride, d.pad, d.dilation, d.compute = kind, N, k, k, s, p, 1, compute
+    keep = [w.to(DEV)]
+    if kind == _lib.CONV_DGRAD:                        # the gradient's descriptor reads dy (OH x OW) and writes the forward input's extent
+        d.IH, d.IW, d.OH, d.OW = OH, OW, H, W
+        dy = rnd(N, cout, OH, OW, seed=10)
+        ref = F.conv_transpose2d(dy.double(), w.double(), None, s, p)
+        ins, out_c, out_hw = [(dy, cout, False)], cin, (H, W)
+    else:
+        d.IH, d.IW, d.OH, d.OW = H, W, OH, OW
+        xs = [rnd(N, c, H, W, lo=lo, seed=10 + i) for i, (c, _) in enumerate(pieces)]
+        bias = rnd(cout, seed=2)
+        keep.append(bias.to(DEV))
+        d.bias = keep[-1].data_ptr()
+        x64 = torch.cat(xs, 1).double()
+        ref = F.conv_transpose2d(x64, w.double(), bias.double(), s, p) if transposed else F.conv2d(x64, w.double(), bias.double(), s, p)
+        ins, out_c, out_hw = [(x, c, planar) for x, (c, planar) in zip(xs, pieces)], cout, (OH, OW)
+    d.n_in = len(ins)
+    for o, (x, c, planar) in zip(d.in_, ins):
+        h_, w_ = x.shape[2:]
+        t = x.contiguous().to(DEV) if planar else nhwc(x)
+        keep.append(t)
+        o.data, o.C = t.data_ptr(), c
+        o.stride_n, o.stride_c, o.stride_h, o.stride_w = (c * h_ * w_, h_ * w_, w_, 1) if planar else (h_ * w_ * c, 1, w_ * c, c)
+    y = torch.zeros(N, out_hw[0], out_hw[1], out_c, device=DEV)
+    d.n_out = 1
+    r = d.out[0]
+    r.data, r.C, r.stride_w, r.stride_h, r.stride_n = y.data_ptr(), out_c, out_c, out_hw[1] * out_c, out_hw[0] * out_hw[1] * out_c
+    assert tuple(ref.shape) == (N, out_c) + out_hw
+    recip = None
+    if route == "head_fwd":
+        assert lib.dn_conv_fwd_fuses_reciprocal(C.byref(d)) == 1
+        recip = torch.zeros(N, OH, OW, 1, device=DEV)
+        d.recip_out = recip.data_ptr()
+    n = lib.dn_conv_packed_weight_elems(C.byref(d))
+    assert n > 0, _lib.last_error()
+    wp = torch.zeros(n, device=DEV)
+    d.w_packed = wp.data_ptr()
+    stream = torch.cuda.current_stream().cuda_stream
+    _lib.call("dn_conv_pack_weights", C.byref(d), keep[0].data_ptr(), wp.data_ptr(), stream)
+    assert lib.dn_debug_conv_route(C.byref(d)).decode() == route
+    _lib.call({_lib.CONV_FWD: "dn_conv2d_fwd", _lib.CONV_DGRAD: "dn_conv2d_dgrad", _lib.CONVT_FWD: "dn_convT2d_fwd"}[kind], C.byref(d), stream)
+    kernel = lib.dn_last_kernel().decode()
+    torch.cuda.synchronize()
+    assert kernel.startswith(ROUTE_KERNELS[route]), kernel
+    rel = _rel_l2(nchw(y), ref)
+    print("%s: %s, relative L2 against fp64 %.3g" % (route, kernel, rel))
+    assert rel <= REL_L2, (kernel, rel)
+    if recip is not None:
+        want = 1.0 / y.double()
+        ulp = torch.pow(2.0, torch.floor(torch.log2(want.abs())) - 23)
+        assert bool(((recip.double() - want).abs() <= ulp).all())
