@@ -68,8 +68,6 @@ struct Knobs {
   bool no_x3_direct, no_x3_wgrad;        // DN_NO_X3_DIRECT / DN_NO_X3_WGRAD: the fp32 matrix instruction in the direct forward family / tiled weight gradient
   bool no_tap_windows;                   // DN_NO_TAP_WINDOWS: > 32-tap weight gradients on the unscheduled kernel
   int wino_wgw;                          // DN_WINO_WGW: 0 = keep the 64 x 64 x 16-position weight-gradient block where 128 x 64 x 8 would run (bitwise test)
-  int wino_dbg, wino_wg_dbg, lds3_dbg;   // DN_WINO_DBG / DN_WINO_WG_DBG / DN_LDS3_DBG: timing / ablation instantiations (tools/wino_timing.py, tools/lds3_timing.py)
-  unsigned long long wino_dbgptr;        // DN_WINO_DBGPTR: where they write their time stamps
   int wino_min_tiles;                    // DN_WINO_MIN_TILES: fewest 2x2 output tiles the Winograd kernels take (192)
   int wino_splitk_target, wino_splitk_maxblocks;   // DN_WINO_SPLITK_TARGET (512 blocks) / _MAXBLOCKS (208): the 4-wave kernel's K split of small grids
   int pack_blocks;                       // DN_PACK_BLOCKS: blocks per table entry of the batched weight re-lay (x2 for the Winograd entries)
@@ -77,7 +75,6 @@ struct Knobs {
   int wino_nmajor;                       // DN_WINO_NMAJOR (1): Winograd forward/dgrad tile order within an XCD: 1 tile row fastest (one 64-cout weight slice per XCD), 0 cout slice fastest, 2/3 by slice count
   int wino_wg_target;                    // DN_WINO_WG_TARGET (0 = by rule: 128 for small layers, else 256): blocks per round the Winograd weight gradient's tile split aims at
   int wino8;                             // DN_WINO8 (0 never / 1 always / -1 = by rule): 8-wave three-piece Winograd kernel
-  int wino8_var;                         // DN_WINO8_VAR: main-loop variant of the 8-wave kernel (A/B measurements)
 };
 const Knobs& knobs();
 

@@ -22,8 +22,6 @@ namespace dn {
 struct WgGeo {
   int tilesX, tilesY, ntiles, per_xcd;
   long long slab;                  // floats per block slab of the workspace: Npad * Kp
-  int dbgmode;                     // DN_LDS3_DBG value: 2 = no loads, 3 = loads from a 64 KB window (timing ablations, wrong results)
-  long long* dbg;                  // DN_LDS3_DBG=1 (tools/lds3_timing.py): per-wave phase ticks, 8 per wave; nullptr otherwise
 };
 
 constexpr int WG_TH = 8, WG_TW = 32;
@@ -36,7 +34,7 @@ constexpr int WG_XPIECE = 16 * WG_XSTR;
 constexpr int WG_DCOLS = 36;                      // fp32 plane of the 1-channel piece: [10][36], column c at c + 1
 constexpr int WG16_LDS = 3 * WG_GPIECE + 3 * WG_XPIECE + 10 * WG_DCOLS * 4;
 
-template <bool HAS1, bool DBG = false>
+template <bool HAS1>
 __global__ void __launch_bounds__(256, 2) lds3_wgrad16_kernel(const IgemmParams p, const WgGeo geo) {
   extern __shared__ __align__(16) char lds[];
   char* Gp = lds;
@@ -140,20 +138,11 @@ __global__ void __launch_bounds__(256, 2) lds3_wgrad16_kernel(const IgemmParams 
   const int xcd = (int)blockIdx.x & 7, local = (int)blockIdx.x >> 3, nlocal = (int)gridDim.x >> 3;
   const int band_lo = xcd * geo.per_xcd, band_hi = min(band_lo + geo.per_xcd, geo.ntiles);
   constexpr int AS[6] = {0, 0, 1, 0, 1, 2}, BS[6] = {2, 1, 1, 0, 0, 0};
-  long long tk[6] = {0, 0, 0, 0, 0, 0}, c0t = 0, c1t = 0;             // DBG: load wait | split + LDS writes | barrier | load issue | matrix loop | barrier
-  auto stamp = [&](int k) __attribute__((always_inline)) {
-    if constexpr (DBG) { c1t = clock64(); tk[k] += c1t - c0t; c0t = c1t; }
-  };
   if (band_lo + local < band_hi) issue_loads(band_lo + local);
-  if constexpr (DBG) c0t = clock64();
   for (int t = band_lo + local; t < band_hi; t += nlocal) {
-    if constexpr (DBG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(0); }
     store_lds();
-    stamp(1);
     __syncthreads();
-    stamp(2);
     if (t + nlocal < band_hi) issue_loads(t + nlocal);
-    stamp(3);
 #pragma unroll 1
     for (int rr = 0; rr < 2; ++rr) {
       const int r = 2 * wave + rr;                                   // this wave's K-step: tile row r, pixels 8 g .. 8 g + 7 per lane group
@@ -202,16 +191,7 @@ __global__ void __launch_bounds__(256, 2) lds3_wgrad16_kernel(const IgemmParams 
         for (int q = 0; q < 6; ++q) acc[9] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[AS[q]], b[BS[q]], acc[9], 0, 0, 0);
       }
     }
-    stamp(4);
     __syncthreads();
-    stamp(5);
-  }
-  if constexpr (DBG) {
-    if (lane == 0) {
-      long long* o = geo.dbg + ((size_t)blockIdx.x * 8 + wave) * 8;
-      for (int k = 0; k < 6; ++k) o[k] = tk[k];
-      o[6] = (band_hi - band_lo - local + nlocal - 1) / nlocal;
-    }
   }
 
   // ---- the four waves meet (fixed order) and the block writes its slab ws[block][co][k], k = tap * 16 + ci (operand 0), kbase1 + tap
@@ -425,15 +405,9 @@ int launch_lds3_wgrad(const dn_conv_desc* d, IgemmParams& p, float* dw, hipStrea
   geo.ntiles = p.N * geo.tilesX * geo.tilesY;
   geo.per_xcd = (geo.ntiles + 7) / 8;
   geo.slab = (long long)p.Npad * p.ph[0].nchunks * kChunk;
-  geo.dbg = knobs().lds3_dbg ? reinterpret_cast<long long*>(knobs().wino_dbgptr) : nullptr;
-  geo.dbgmode = knobs().lds3_dbg;
   const int blocks = lds3_wgrad_blocks(p);
   hipError_t e = hipSuccess;
-  if (geo.dbg != nullptr && form == 2) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(lds3_wgrad16_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, WG16_LDS);
-    if (e == hipSuccess) DN_LAUNCH((lds3_wgrad16_kernel<true, true>), dim3(blocks), dim3(256), (size_t)WG16_LDS, stream, p, geo);
-    set_last_kernel("dn::lds3_wgrad16_kernel<true>");
-  } else if (form == 3) {
+  if (form == 3) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(lds3_wgrad_stem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
     if (e == hipSuccess) DN_LAUNCH(lds3_wgrad_stem_kernel, dim3(blocks), dim3(256), (size_t)WGS_LDS, stream, p, geo);
     set_last_kernel("dn::lds3_wgrad_stem_kernel");
@@ -478,7 +452,7 @@ constexpr int WK_NCI = 96;
 constexpr int WK_XPIECE = WK_NCI * WK_XSTR;
 constexpr int WK_LDS = 3 * WK_GPIECE + 3 * WK_XPIECE + WK_XROWS * WG_DCOLS * 4;
 
-template <bool HAS1, bool DBG = false>
+template <bool HAS1>
 __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p, const WgGeo geo, int c0) {
   extern __shared__ __align__(16) char lds[];
   char* Gp = lds;
@@ -515,10 +489,10 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
   // dy job = (row 0..1, column group 0..3, channel quad 0..7) -> 64: round B, threads 64..127.  The jobs of the first operand come first
   // (24 x c0 / 4 of them, a whole number of waves: lds3k_wgrad_form), quad fastest within an operand: every wave reads ONE operand through
   // ONE descriptor (a per-lane choice needs two loads with complementary predicates and an add that waits for both: 8 k of the tile's 21 k
-  // ticks went there, tools/lds3_timing.py) and a pixel's channels stay contiguous across its lanes.
+  // ticks went there, in-kernel phase timestamps) and a pixel's channels stay contiguous across its lanes.
   // Within an operand a job index reads (rc / 4, quad / 4, quad % 4, rc % 4) from the top: sixteen consecutive lanes write four channel
   // quads x four neighbouring 16-byte columns, which are sixteen different bank groups (planes 400 bytes apart: the quad moves the
-  // column by 4 of 16, rc by one); quad-fastest lanes collided four deep (3.2-3.7 k ticks of staging against 2.1 k, tools/lds3_timing.py).
+  // column by 4 of 16, rc by one); quad-fastest lanes collided four deep (3.2-3.7 k ticks of staging against 2.1 k, likewise).
   const int nq0 = two ? c0 >> 2 : 24, n0jobs = 24 * nq0;
   auto decode = [&](int job, int& quad, int& rc, bool& second) __attribute__((always_inline)) {
     second = job >= n0jobs;
@@ -536,7 +510,7 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
   // Job A = this thread's x job; job B = the 64 remaining x jobs (wave 2) and the 64 dy jobs (wave 3).  The offsets of the NEXT tile are
   // prepared once per tile and the sixteen loads are issued ONE AT A TIME between the groups of the matrix loop (load_site): the texture
   // path takes a tile's 82 KB in ~2-3 k cycles, and a wave that issues its loads in one piece stands in that queue with its matrix
-  // instructions behind it (tools/lds3_timing.py: 3 k of 14.8 k ticks per tile, whether ahead of the loop or at the top of a K-step).
+  // instructions behind it (phase timestamps: 3 k of 14.8 k ticks per tile, whether ahead of the loop or at the top of a K-step).
   const bool secAu = __builtin_amdgcn_readfirstlane((int)secA) != 0, secBu = __builtin_amdgcn_readfirstlane((int)secB) != 0;
   const int waveu = __builtin_amdgcn_readfirstlane(wave);
   const bool hasB = waveu == 2 || waveu == 3;
@@ -587,10 +561,6 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
       offD = ok ? (n * (int)SD.sn + (iy >> SD.up) * (int)SD.sh + (ix >> SD.up) * (int)SD.sw) * 4 : -1;
     }
     if (!live) { maskA = 0; maskB = 0; offD = -1; }
-    if constexpr (DBG) {
-      if (geo.dbgmode == 2) { maskA = 0; maskB = 0; }
-      if (geo.dbgmode == 3) { offA &= 0xfff0; offB &= 0xfff0; stepA = 16; stepB = 16; }
-    }
   };
   auto load_site = [&](int i) __attribute__((always_inline)) {          // pixel i of both jobs (i is a compile-time constant at every site)
     va[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rA, (maskA >> i) & 1 ? offA + i * stepA : -1, 0, 0));
@@ -638,23 +608,15 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
   const int xcd = (int)blockIdx.x & 7, local = (int)blockIdx.x >> 3, nlocal = (int)gridDim.x >> 3;
   const int band_lo = xcd * geo.per_xcd, band_hi = min(band_lo + geo.per_xcd, geo.ntiles);
   constexpr int AS[6] = {0, 0, 1, 0, 1, 2}, BS[6] = {2, 1, 1, 0, 0, 0};
-  long long tk[6] = {0, 0, 0, 0, 0, 0}, c0t = 0, c1t = 0;             // DBG: load wait | split + LDS writes | barrier | load issue | matrix loop | barrier
-  auto stamp = [&](int k) __attribute__((always_inline)) {
-    if constexpr (DBG) { c1t = clock64(); tk[k] += c1t - c0t; c0t = c1t; }
-  };
   if (band_lo + local < band_hi) {
     prep_loads(band_lo + local, true);
 #pragma unroll
     for (int i = 0; i < 8; ++i) load_site(i);
     load_d();
   }
-  if constexpr (DBG) c0t = clock64();
   for (int t = band_lo + local; t < band_hi; t += nlocal) {
-    if constexpr (DBG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(0); }
     store_lds();
-    stamp(1);
     __syncthreads();
-    stamp(2);
     const bool more = t + nlocal < band_hi;
     if (more) {
       prep_loads(t + nlocal, true);
@@ -662,7 +624,6 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
       for (int i = 0; i < 8; ++i) load_site(i);
       load_d();
     }
-    stamp(3);
 #pragma unroll
     for (int r = 0; r < WK_TH; ++r) {                                  // K-step: tile row r, pixels 8 g .. 8 g + 7 per lane group
       bf16x8 a[2][3];
@@ -722,16 +683,7 @@ __global__ void __launch_bounds__(512, 2) lds3k_wgrad_kernel(const IgemmParams p
         }
       }
     }
-    stamp(4);
     __syncthreads();
-    stamp(5);
-  }
-  if constexpr (DBG) {
-    if (lane == 0) {
-      long long* o = geo.dbg + ((size_t)blockIdx.x * 8 + wave) * 8;
-      for (int k = 0; k < 6; ++k) o[k] = tk[k];
-      o[6] = (band_hi - band_lo - local + nlocal - 1) / nlocal;
-    }
   }
 
   // ---- every wave owns its columns: straight into the block's slab ws[block][co][k]
@@ -825,13 +777,7 @@ int launch_lds3k_wgrad(const dn_conv_desc* d, IgemmParams& p, float* dw, hipStre
   const int blocks = lds3k_wgrad_blocks(p);
   const int c0 = p.in[0].C;
   hipError_t e = hipSuccess;
-  geo.dbg = knobs().lds3_dbg ? reinterpret_cast<long long*>(knobs().wino_dbgptr) : nullptr;
-  geo.dbgmode = knobs().lds3_dbg;
-  if (geo.dbg != nullptr && form == 2) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(lds3k_wgrad_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, WK_LDS);
-    if (e == hipSuccess) DN_LAUNCH((lds3k_wgrad_kernel<true, true>), dim3(blocks), dim3(512), (size_t)WK_LDS, stream, p, geo, c0);
-    set_last_kernel("dn::lds3k_wgrad_kernel<true>");
-  } else if (form == 2) {
+  if (form == 2) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(lds3k_wgrad_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, WK_LDS);
     if (e == hipSuccess) DN_LAUNCH(lds3k_wgrad_kernel<true>, dim3(blocks), dim3(512), (size_t)WK_LDS, stream, p, geo, c0);
     set_last_kernel("dn::lds3k_wgrad_kernel<true>");

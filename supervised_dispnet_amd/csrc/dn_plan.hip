@@ -87,11 +87,7 @@ static void read_knobs(Knobs* k) {
   k->no_thin = on("DN_NO_THIN");
   k->no_thin_conv = on("DN_NO_THIN_CONV");
   k->no_splitk = on("DN_NO_SPLITK");
-  k->wino_dbg = num("DN_WINO_DBG", 0);
-  k->wino_wg_dbg = num("DN_WINO_WG_DBG", 0);
   k->wino_wgw = num("DN_WINO_WGW", 1);
-  k->lds3_dbg = num("DN_LDS3_DBG", 0);
-  k->wino_dbgptr = getenv("DN_WINO_DBGPTR") ? strtoull(getenv("DN_WINO_DBGPTR"), nullptr, 0) : 0ull;
   k->wino_min_tiles = num("DN_WINO_MIN_TILES", 192);
   k->no_x3_direct = on("DN_NO_X3_DIRECT");
   k->no_wino_splitk = on("DN_NO_WINO_SPLITK");
@@ -108,7 +104,6 @@ static void read_knobs(Knobs* k) {
   k->wino_nmajor = num("DN_WINO_NMAJOR", 1);
   k->no_riding_fences = on("DN_NO_RIDING_FENCES");
   k->wino8 = num("DN_WINO8", -1);
-  k->wino8_var = num("DN_WINO8_VAR", 0);
 }
 
 const Knobs& knobs() {

@@ -298,7 +298,6 @@ int launch_wino_pack16(const IgemmParams& p, const float* w, float* wp, int piec
 // Packed layout of a layer wino_eligible takes.  1: fp32 Winograd; 2: bf16-multiply Winograd (descriptor compute = DN_COMPUTE_BF16); 3: fp32 products from
 // three bf16 pieces per operand (DN_COMPUTE_F32X3) -- the last two on the default tile variant only
 int wino_layout(const IgemmParams& p) {
-  if (knobs().wino_dbg != 0 && knobs().wino_dbg != 4 && knobs().wino_dbg < 16) return 1;
   if (p.compute == DN_COMPUTE_F32X3) return 3;          // (either tile height)
   return p.compute == DN_COMPUTE_BF16 ? 2 : 1;
 }
@@ -340,7 +339,7 @@ int launch_wino_pack(const IgemmParams& p, const float* w, float* wp, hipStream_
 // LDS nor 48 registers of pending pieces); the weights are packed as three pieces; SIX matrix instructions per (position, 32 couts):
 // x0y2, x2y0, x1y1, x1y0, x0y1, x0y0 -- 48 per chunk = 1536 cycles against the 4096 of the fp32 instruction, and unlike that one they
 // leave the vector ALUs to the wave: ~6 vector instructions issue under each of them (tools/ubench/agpr_issue.hip).
-template <int MTW, bool HA, int DBG, int PREC = 0>     // PREC 0: fp32 matrix instruction, 1: bf16 operands, 3: three bf16 pieces per operand
+template <int MTW, bool HA, int PREC = 0>     // PREC 0: fp32 matrix instruction, 1: bf16 operands, 3: three bf16 pieces per operand
 __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const IgemmParams p) {
   constexpr bool BF = PREC != 0;
   static_assert(PREC != 1 || MTW == 1, "the bf16-rounded variant exists for the two-blocks-per-CU tile only");
@@ -370,8 +369,6 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
       g1 = g0 + cps < p.ks_chunks ? g0 + cps : p.ks_chunks;
     }
   }
-  long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, te1 = 0, te2 = 0;
-  if (DBG & 4) t0 = clock64();
 
   // ---- staging role: one 4x4 patch of VW channels per thread and chunk: 64 tiles x 4 float4 groups, or 32 tiles x 8 float2
   //      groups (the narrow variant keeps the patch in 32 registers: its budget is 128 next to the 128 accumulators)
@@ -573,15 +570,8 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
 
     // ---- pipeline fill for this operand (one exposed memory latency + transform per operand)
     {
-      if constexpr (DBG & 128) {            // ablation: what a prologue without its exposed memory latency would cost (timing only)
 #pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-          for (int e = 0; e < VW; ++e) v[i][e] = 1.f;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) load_v(i);
-      }
+      for (int i = 0; i < 16; ++i) load_v(i);
       load_aff();
       if (first_op) {
         first_op = false;
@@ -607,7 +597,6 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
       }
     }
     __syncthreads();
-    if (DBG & 4) t1 = clock64();
 
     if constexpr (PREC == 3) {
       // One chunk = 48 matrix instructions (slot m = 12 j + 2 t + half); the side work of a slot is what the wave issues while that
@@ -625,13 +614,6 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
       };
       auto split_pair = [&](int slot, int mm, int q) {  // channels 2q, 2q+1 of the fragment of tile half mm: x = h + m + l exactly
         const f32x2 x = f32x2{raw[mm][q >> 1][2 * (q & 1)], raw[mm][q >> 1][2 * (q & 1) + 1]};
-        if constexpr (DBG & 16) {                       // ablation (timing only, wrong results): no split arithmetic
-          const bf16x2 h = __builtin_convertvector(x, bf16x2);
-          fa3[slot][mm][0][2 * q] = h[0]; fa3[slot][mm][0][2 * q + 1] = h[1];
-          fa3[slot][mm][1][2 * q] = h[1]; fa3[slot][mm][1][2 * q + 1] = h[0];
-          fa3[slot][mm][2][2 * q] = h[0]; fa3[slot][mm][2][2 * q + 1] = h[0];
-          return;
-        }
         const bf16x2 h = __builtin_convertvector(x, bf16x2);
         const f32x2 r1 = x - __builtin_convertvector(h, f32x2);
         const bf16x2 m = __builtin_convertvector(r1, bf16x2);
@@ -664,35 +646,34 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
           constexpr int AS[6] = {0, 0, 1, 0, 1, 2}, BS[6] = {2, 1, 1, 0, 0, 0};
           acc[j][mm][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa3[j & 1][mm][AS[t]], bq[(3 * u + 2 - BS[t]) % WRING], acc[j][mm][nn], 0, 0, 0);
           // ---- side work of this slot
-          if constexpr (!(DBG & 32) && mm == 0) {                  // (DBG 32: ablation without the weight stream)
+          if constexpr (mm == 0) {
             if constexpr (t == 1) load_b3(3 * u + WRING);          // piece 2 of this unit was released by the instructions t = 0
             if constexpr (t == 3) load_b3(3 * u + 1 + WRING);      // piece 1 by t = 2
             if constexpr (t == 0 && m > 0) load_b3(3 * (u - 1) + 2 + WRING);     // piece 0 of the previous unit by its last instruction
           }
           if constexpr (j < 3 && q12 == 1) read_raw(Ab, j + 1);
           if constexpr (j < 3 && q12 >= 6 * MTW && q12 < 10 * MTW) split_pair((j + 1) & 1, (q12 - 6 * MTW) / 4, (q12 - 6 * MTW) % 4);
-          constexpr bool STG = !(DBG & 64);                       // (DBG 64: ablation without the staging of the next chunk)
-          if constexpr (MTW == 1 && !(DBG & 256)) {
+          if constexpr (MTW == 1) {
             // round 3 (measured on the 8-wave form, dn_winograd8.hip): the 16 patch loads on every OTHER slot instead of back to back --
             // a wave whose load finds the vector-memory queue full stalls in order, with its matrix instructions behind it --, the
             // clamp / row / column transform + stores packed into the last fourteen slots
-            if constexpr (STG && m >= 1 && m < 33 && (m & 1)) load_v_t((m - 1) / 2, std::false_type{}, lmask);
-            if constexpr (STG && m == 2) load_aff();
-            if constexpr (STG && m >= 34 && m < 38) {
+            if constexpr (m >= 1 && m < 33 && (m & 1)) load_v_t((m - 1) / 2, std::false_type{}, lmask);
+            if constexpr (m == 2) load_aff();
+            if constexpr (m >= 34 && m < 38) {
 #pragma unroll
               for (int u4 = 0; u4 < 4; ++u4) affine_piece(4 * (m - 34) + u4);
             }
-            if constexpr (STG && m >= 38 && m < 40) {
+            if constexpr (m >= 38 && m < 40) {
               row_piece(2 * (m - 38));
               row_piece(2 * (m - 38) + 1);
             }
-            if constexpr (STG && m >= 40 && m < 48) col_piece(buf ^ 1, (m - 40) / 2, (m - 40) % 2);
+            if constexpr (m >= 40 && m < 48) col_piece(buf ^ 1, (m - 40) / 2, (m - 40) % 2);
           } else {
-          if constexpr (STG && m >= 2 && m < 18) load_v_t(m - 2, std::false_type{}, lmask);
-          if constexpr (STG && m == 18) load_aff();
+          if constexpr (m >= 2 && m < 18) load_v_t(m - 2, std::false_type{}, lmask);
+          if constexpr (m == 18) load_aff();
           // transform + stores of the next chunk: 16 affine pieces, 4 row pieces, 8 column pieces from slot 22 MTW on
           constexpr int A0 = 22 * MTW, R0 = A0 + 8 * MTW, C0 = R0 + 4;
-          if constexpr (STG && m >= A0 && m < R0) {
+          if constexpr (m >= A0 && m < R0) {
             if constexpr (MTW == 1) {
               affine_piece(2 * (m - A0));
               affine_piece(2 * (m - A0) + 1);
@@ -700,12 +681,12 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
               affine_piece(m - A0);
             }
           }
-          if constexpr (STG && m >= R0 && m < R0 + 4) row_piece(m - R0);
-          if constexpr (STG && m >= C0 && m < C0 + 8) col_piece(buf ^ 1, (m - C0) / 2, (m - C0) % 2);
+          if constexpr (m >= R0 && m < R0 + 4) row_piece(m - R0);
+          if constexpr (m >= C0 && m < C0 + 8) col_piece(buf ^ 1, (m - C0) / 2, (m - C0) % 2);
           }
           __builtin_amdgcn_sched_barrier(0);
         });
-        if constexpr (!(DBG & 32)) load_b3(3 * 7 + 2 + WRING);      // successor of the last unit's piece 0
+        load_b3(3 * 7 + 2 + WRING);      // successor of the last unit's piece 0
         wcur16 += wchunk16B;
         __syncthreads();
         buf ^= 1;
@@ -789,7 +770,6 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
     }
   }
 
-  if (DBG & 4) t2 = clock64();
   // ---- output transform.  Along j in registers:  Z[b] = sum_j A^T[b][j] M[i][j],  A^T = (1 1 1 0 / 0 1 -1 -1)
   f32x16 Z[2][MTW][2];
 #pragma unroll
@@ -872,7 +852,6 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
     }
   }
 
-  if (DBG & 4) te1 = clock64();
   // ---- batch statistics of the pre-bias result: partial row MTW*mb + m covers tiles [32(MTW*mb+m), +32) = 128 pixels;
   //      (sum, M2 about the group's own mean), merged by dn_bn_finalize
   const int n_first = nb * WBN + 4 * c4;
@@ -959,11 +938,10 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
   if (p.bnb_y != nullptr)                // (input gradient: the BatchNorm backward's column sums of the layer below)
     wino_bn_bwd_sums<NK, 16, 4, MTW>(p, Y, mb, tg, c4, wave, lane, tid, n_first, smem + 4 * BT * WZLD);
 
-  if (DBG & 4) te2 = clock64();
   // ---- bias, activation, channel-split / accumulating stores: float4 along the channels when the four columns lie in one
   //      float4-addressable result, element-wise otherwise (the 1-channel disparity piece of a concat's input gradient)
   // Every vector instruction of this phase is issued between the PARTNER block's MFMAs (one slot per 64 cycles while it is in its main
-  // loop -- measured with DN_WINO_DBG=4/12: 11.4 k of the epilogue's 14 k ticks were spent here, with or without the stores), so the
+  // loop -- measured with in-kernel timestamps: 11.4 k of the epilogue's 14 k ticks were spent here, with or without the stores), so the
   // common case is kept to a minimum of instructions: one address per tile, constant offsets for its four pixels, the result
   // selection / activation / accumulate decisions taken once, outside the loops.
   if (n_first < p.Ntot) {
@@ -1017,12 +995,10 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
             v[1][0] += g10;
             v[1][1] += g11;
           }
-          if (!(DBG & 8) || v[0][0][0] == 12345.678f) {      // DBG 8: ablation without the stores
-            *reinterpret_cast<f32x4*>(o00) = v[0][0];
-            *reinterpret_cast<f32x4*>(o00 + sw) = v[0][1];
-            *reinterpret_cast<f32x4*>(o00 + rowB) = v[1][0];
-            *reinterpret_cast<f32x4*>(o00 + rowB + sw) = v[1][1];
-          }
+          *reinterpret_cast<f32x4*>(o00) = v[0][0];
+          *reinterpret_cast<f32x4*>(o00 + sw) = v[0][1];
+          *reinterpret_cast<f32x4*>(o00 + rowB) = v[1][0];
+          *reinterpret_cast<f32x4*>(o00 + rowB + sw) = v[1][1];
         }
       }
     } else {
@@ -1059,25 +1035,16 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
       }
     }
   }
-  if (DBG & 4) {
-    t3 = clock64();
-    if (tid == 0) {
-      long long* o = reinterpret_cast<long long*>(p.ws) + (size_t)blockIdx.x * 8;
-      o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3; o[4] = te1; o[5] = te2;
-    }
-  }
-  if constexpr (DBG == 0) {
-    if (p.fold_bn | p.fold_bnb) {
-      // (tile coordinates recomputed from a laundered block index: keeping nb / MT alive across the whole kernel for this tail cost the
-      //  variant with a pending BatchNorm five spilled registers)
-      __syncthreads();                   // (the LDS of the epilogue is free from here)
-      unsigned bx = blockIdx.x;
-      asm volatile("" : "+s"(bx));
-      const int MT2 = (p.T + BT - 1) / BT, NT2 = p.Npad / WBN;
-      const int per2 = (MT2 * NT2 + 7) >> 3;
-      const int q2 = (int)(bx & 7u) * per2 + (int)(bx >> 3);
-      wino_fold_tail(p, p.nmajor ? q2 / MT2 : q2 % NT2, MT2, smem, (int)threadIdx.x);
-    }
+  if (p.fold_bn | p.fold_bnb) {
+    // (tile coordinates recomputed from a laundered block index: keeping nb / MT alive across the whole kernel for this tail cost the
+    //  variant with a pending BatchNorm five spilled registers)
+    __syncthreads();                     // (the LDS of the epilogue is free from here)
+    unsigned bx = blockIdx.x;
+    asm volatile("" : "+s"(bx));
+    const int MT2 = (p.T + BT - 1) / BT, NT2 = p.Npad / WBN;
+    const int per2 = (MT2 * NT2 + 7) >> 3;
+    const int q2 = (int)(bx & 7u) * per2 + (int)(bx >> 3);
+    wino_fold_tail(p, p.nmajor ? q2 / MT2 : q2 % NT2, MT2, smem, (int)threadIdx.x);
   }
 }
 
@@ -1085,17 +1052,17 @@ __global__ void __launch_bounds__(256, MTW == 2 ? 1 : 2) wino_conv_kernel(const 
 // blocks: asked for by the caller, few enough partial rows for one block per 64 channels, counters available.
 bool wino_folds_bn_finalize(const IgemmParams& p) {
   return p.bnf.scale != nullptr && p.bn_partial != nullptr && p.fold_cnt != nullptr && (p.T + 31) / 32 <= kFoldMaxRows &&
-         wino_npad(p) / WBN <= kFoldCounters && knobs().wino_dbg == 0;
+         wino_npad(p) / WBN <= kFoldCounters;
 }
 bool wino_folds_bn_sums(const IgemmParams& p) {
   return p.bnb_dgamma != nullptr && p.bnb_dbeta != nullptr && p.bnb_partial != nullptr && p.fold_cnt != nullptr && (p.T + 31) / 32 <= kFoldMaxRows &&
-         wino_npad(p) / WBN <= kFoldCounters && knobs().wino_dbg == 0;
+         wino_npad(p) / WBN <= kFoldCounters;
 }
 
-template <int MTW, bool HA, int DBG, int PREC = 0>
+template <int MTW, bool HA, int PREC = 0>
 static int launch_wino_variant(const IgemmParams& p, hipStream_t stream) {
   using Cfg = WinoCfg<MTW>;
-  auto kernel = wino_conv_kernel<MTW, HA, DBG, PREC>;
+  auto kernel = wino_conv_kernel<MTW, HA, PREC>;
   // PREC 1: two 16-channel chunks of bf16 planes, or the epilogue's cross-wave exchange + statistics scratch, whichever is larger
   constexpr size_t lds16a = (size_t)2 * 16 * Cfg::BT * W16_ROWB;
   constexpr size_t lds16b = (size_t)(4 * Cfg::BT * WZLD + MTW * 8 * 64) * sizeof(float);
@@ -1108,7 +1075,7 @@ static int launch_wino_variant(const IgemmParams& p, hipStream_t stream) {
   const int tiles = ((p.T + Cfg::BT - 1) / Cfg::BT) * (p.Npad / WBN);
   dim3 grid((tiles + 7) / 8 * 8, (PREC == 3 && MTW == 1 && p.ksplit > 1) ? p.ksplit : 1);
   DN_LAUNCH(kernel, grid, dim3(256), lds, stream, p);
-  set_last_kernel("dn::wino_conv_kernel<%d, %s, %d, %d>", MTW, HA ? "true" : "false", DBG, PREC);
+  set_last_kernel("dn::wino_conv_kernel<%d, %s, %d>", MTW, HA ? "true" : "false", PREC);
   return check_launch("wino_conv_kernel");
 }
 
@@ -1132,44 +1099,22 @@ int launch_wino_conv(IgemmParams& p, hipStream_t stream) {
   }
   p.fold_bn = wino_folds_bn_finalize(p) ? 1 : 0;
   p.fold_bnb = wino_folds_bn_sums(p) ? 1 : 0;
-  const int dbg = knobs().wino_dbg;
   if (p.compute == DN_COMPUTE_BF16)      // (wino_layout() has checked that the bf16 variants may be used)
-    return p.any_affine ? launch_wino_variant<1, true, 0, 1>(p, stream) : launch_wino_variant<1, false, 0, 1>(p, stream);
+    return p.any_affine ? launch_wino_variant<1, true, 1>(p, stream) : launch_wino_variant<1, false, 1>(p, stream);
   p.ksplit = 1;
   if (p.compute == DN_COMPUTE_F32X3) {
-    if ((knobs().wino_dbg == 0 || (knobs().wino_dbg & 4)) && wino8_wanted(p)) return launch_wino_conv8(p, stream);
-    if (knobs().wino_dbg == 0) {
-      // few blocks, long K: split the input channels.  Needs the caller's workspace (dn_conv_desc.splitk_ws)
-      const int ks = wino_splitk_choice(p);
-      if (ks > 1 && p.ks_ws != nullptr && p.ks_ws_bytes >= wino_splitk_workspace_bytes(p)) {
-        p.ksplit = ks;
-        p.ks_chunks = wino_ktot(p) / WKC;
-        p.ks_cnt_floats = kSplitKCounterBytes / 4;
-      }
+    if (wino8_wanted(p)) return launch_wino_conv8(p, stream);
+    // few blocks, long K: split the input channels.  Needs the caller's workspace (dn_conv_desc.splitk_ws)
+    const int ks = wino_splitk_choice(p);
+    if (ks > 1 && p.ks_ws != nullptr && p.ks_ws_bytes >= wino_splitk_workspace_bytes(p)) {
+      p.ksplit = ks;
+      p.ks_chunks = wino_ktot(p) / WKC;
+      p.ks_cnt_floats = kSplitKCounterBytes / 4;
     }
     // (the 64-tile / one-block-per-CU form of this variant -- the loop below is written for either tile height -- moves 37 % fewer bytes
     //  through the texture addresser, the weight pieces being fetched once per 64 tiles, and was measured 5-10 % SLOWER on every layer
     //  but one: a single wave per SIMD stalls on every wait)
-    if (knobs().wino_dbg == 4) {           // in-kernel timestamps (tools/wino_timing.py)
-      p.ws = reinterpret_cast<float*>(knobs().wino_dbgptr);
-      return p.any_affine ? launch_wino_variant<1, true, 4, 3>(p, stream) : launch_wino_variant<1, false, 4, 3>(p, stream);
-    }
-    switch (knobs().wino_dbg) {            // 16 / 32 / 64 / 112: timing ablations of the three-piece variant (wrong results)
-      case 16: return p.any_affine ? launch_wino_variant<1, true, 16, 3>(p, stream) : launch_wino_variant<1, false, 16, 3>(p, stream);
-      case 32: return p.any_affine ? launch_wino_variant<1, true, 32, 3>(p, stream) : launch_wino_variant<1, false, 32, 3>(p, stream);
-      case 64: return p.any_affine ? launch_wino_variant<1, true, 64, 3>(p, stream) : launch_wino_variant<1, false, 64, 3>(p, stream);
-      case 112: return p.any_affine ? launch_wino_variant<1, true, 112, 3>(p, stream) : launch_wino_variant<1, false, 112, 3>(p, stream);
-      case 128: return p.any_affine ? launch_wino_variant<1, true, 128, 3>(p, stream) : launch_wino_variant<1, false, 128, 3>(p, stream);
-      default: return p.any_affine ? launch_wino_variant<1, true, 0, 3>(p, stream) : launch_wino_variant<1, false, 0, 3>(p, stream);
-    }
-  }
-  if (dbg == 12) {                       // timestamps + no result stores (ablation, tools/wino_timing.py 12)
-    p.ws = reinterpret_cast<float*>(knobs().wino_dbgptr);
-    return p.any_affine ? launch_wino_variant<1, true, 12>(p, stream) : launch_wino_variant<1, false, 12>(p, stream);
-  }
-  if (dbg == 4) {
-    p.ws = reinterpret_cast<float*>(knobs().wino_dbgptr);
-    return p.any_affine ? launch_wino_variant<1, true, 4>(p, stream) : launch_wino_variant<1, false, 4>(p, stream);
+    return p.any_affine ? launch_wino_variant<1, true, 3>(p, stream) : launch_wino_variant<1, false, 3>(p, stream);
   }
   return p.any_affine ? launch_wino_variant<1, true, 0>(p, stream) : launch_wino_variant<1, false, 0>(p, stream);
 }

@@ -123,7 +123,7 @@ __device__ __forceinline__ f32x2 wg_buffer_load2s(__amdgpu_buffer_rsrc_t r, int 
   return __builtin_bit_cast(f32x2, v);
 }
 
-template <bool HA, int DBG>
+template <bool HA>
 __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p) {
   extern __shared__ __align__(16) float smem[];
   char* smemB = reinterpret_cast<char*>(smem);
@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
       unsigned& pmreq = PH == 0 ? pmA : pmB;
       f32x2 (&vfin)[16] = (PH == 0 || PH == 1) ? vB : vA;  // PH 0: finish vB, PH 1: store vB;  PH 2 / 3: vA
       const unsigned pmfin = (PH == 0 || PH == 1) ? pmB : pmA;
-      if constexpr (REQ && !(DBG & 32)) {
+      if constexpr (REQ) {
         load_patch(vreq, pmreq, c + 4);
         load_grad(c + 2);
       }
@@ -328,7 +328,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
         constexpr int cur = g & 1, nxt = cur ^ 1;
         acc[pp][h][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][h], fb[cur][nn], acc[pp][h][nn], 0, 0, 0);
         // ---- side work of this slot
-        if constexpr (g < 7 && !(DBG & 16)) {
+        if constexpr (g < 7) {
           constexpr int g1 = g + 1;
           constexpr int o = (g1 & 1) * G_PLANE + (g1 >> 1) * 2 * G_ROWB;
           if constexpr (qq == 0) fa[nxt][0] = *reinterpret_cast<const float*>(Gb + o);
@@ -336,11 +336,11 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
           if constexpr (qq == 2) fb[nxt][0] = *reinterpret_cast<const float*>(Vb + o);
           if constexpr (qq == 3) fb[nxt][1] = *reinterpret_cast<const float*>(Vb + o + 128);
         }
-        if constexpr (REQ && !(DBG & 2)) {
+        if constexpr (REQ) {
           if constexpr (m >= 8 && m < 24) affine_piece(vfin, pmfin, m - 8);
           if constexpr (m >= 24 && m < 28) row_piece(vfin, m - 24);
         }
-        if constexpr (!REQ && !(DBG & 4)) {
+        if constexpr (!REQ) {
           if constexpr (m < 8 && (m % 2) == 0) col_piece(vfin, buf ^ 1, m / 2);
           if constexpr (m >= 8 && m < 16 && (m % 2) == 0) g_cols(buf ^ 1, (m - 8) / 2);
         }
@@ -353,7 +353,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
       case 2: body(std::integral_constant<int, 2>{}); break;
       default: body(std::integral_constant<int, 3>{}); break;
     }
-    if (!(DBG & 64)) __syncthreads();
+    __syncthreads();
   }
 
   // ---- partial dU of this split: ws[split][pos][co][ci]
@@ -388,7 +388,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_kernel(const IgemmParams p)
 //     are needed for the operands): a wave requests its next chunk's patch + gradient tile at the top of one chunk and transforms +
 //     stores them during the next one; ONE barrier per chunk, placed after the last read of the current buffer / the last store
 //     into the next one (slot 12 of 24), so that the next chunk's first operands are built under the current chunk's tail.
-template <bool HA, int DBG = 0>     // DBG (timing ablations, wrong results): 1 no transform + stores, 2 no split arithmetic, 4 no global loads, 8 no LDS fragment reads (the split of the never-changing registers is hoisted too), 16 no LDS stores (arithmetic kept), 32 no barrier
+template <bool HA>
 __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams p) {
   extern __shared__ __align__(16) float smem[];
   char* smemB = reinterpret_cast<char*>(smem);
@@ -513,16 +513,12 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
     v[8 + b] = d2 - d1;
     v[12 + b] = d1 - v[12 + b];
   };
-  auto put2 = [&](char* dst, f32x2 val) {
-    if constexpr (DBG & 16) asm volatile("" ::"v"(val));      // (ablation: the arithmetic without the LDS store)
-    else *reinterpret_cast<f32x2*>(dst) = val;
-  };
   auto col_piece = [&](int b2, int i) {
     char* dst = smemB + b2 * G_BUFB + G_OPB + stB + (4 * i) * G_PLANE;
-    put2(dst + 0 * G_PLANE, v[4 * i + 0] - v[4 * i + 2]);
-    put2(dst + 1 * G_PLANE, v[4 * i + 1] + v[4 * i + 2]);
-    put2(dst + 2 * G_PLANE, v[4 * i + 2] - v[4 * i + 1]);
-    put2(dst + 3 * G_PLANE, v[4 * i + 1] - v[4 * i + 3]);
+    *reinterpret_cast<f32x2*>(dst + 0 * G_PLANE) = v[4 * i + 0] - v[4 * i + 2];
+    *reinterpret_cast<f32x2*>(dst + 1 * G_PLANE) = v[4 * i + 1] + v[4 * i + 2];
+    *reinterpret_cast<f32x2*>(dst + 2 * G_PLANE) = v[4 * i + 2] - v[4 * i + 1];
+    *reinterpret_cast<f32x2*>(dst + 3 * G_PLANE) = v[4 * i + 1] - v[4 * i + 3];
   };
   auto g_cols = [&](int b2, int i) {
     char* dst = smemB + b2 * G_BUFB + stB + (4 * i) * G_PLANE;
@@ -531,10 +527,10 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
     else if (i == 1) { u0 = gv[0] + gv[2]; u1 = gv[1] + gv[3]; }
     else if (i == 2) { u0 = gv[0] - gv[2]; u1 = gv[1] - gv[3]; }
     else { u0 = gv[2]; u1 = gv[3]; }
-    put2(dst + 0 * G_PLANE, u0);
-    put2(dst + 1 * G_PLANE, u0 + u1);
-    put2(dst + 2 * G_PLANE, u0 - u1);
-    put2(dst + 3 * G_PLANE, u1);
+    *reinterpret_cast<f32x2*>(dst + 0 * G_PLANE) = u0;
+    *reinterpret_cast<f32x2*>(dst + 1 * G_PLANE) = u0 + u1;
+    *reinterpret_cast<f32x2*>(dst + 2 * G_PLANE) = u0 - u1;
+    *reinterpret_cast<f32x2*>(dst + 3 * G_PLANE) = u1;
   };
 
   // ---- operands of the matrix instructions: per co half h  A1 = (x0, x1), A3 = (x0, x2);  per ci half nn  B1 = (y0, y0),
@@ -549,18 +545,11 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
     const bool isB = (k == 0 || k == 3 || k == 4 || k == 7);
     const int pp = (k >= 2 && k <= 5) ? 1 : 0, half = (k == 0 || k == 1 || k == 4 || k == 5) ? 1 : 0;
     const char* base = (k >= 6 ? nxt : cur) + (isB ? G_OPB : 0) + pp * G_PLANE + half * 128;
-    if constexpr (DBG & 8) return;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) raw[k & 1][ks] = *reinterpret_cast<const float*>(base + ks * 2 * G_ROWB);
   };
   auto split_half = [&](int k, int hf, unsigned (&P)[3][2]) {          // tiles (2 hf, 2 hf + 1) of the fragment: x = P0 + P1 + P2 exactly
     const f32x2 x = f32x2{raw[k & 1][2 * hf], raw[k & 1][2 * hf + 1]};
-    if constexpr (DBG & 2) {
-      P[0][hf] = __builtin_bit_cast(unsigned, x[0]);
-      P[1][hf] = __builtin_bit_cast(unsigned, x[1]);
-      P[2][hf] = __builtin_bit_cast(unsigned, x[0]) ^ 0x11u;
-      return;
-    }
     const bf16x2 h = __builtin_convertvector(x, bf16x2);
     const f32x2 r1 = x - __builtin_convertvector(h, f32x2);
     const bf16x2 m = __builtin_convertvector(r1, bf16x2);
@@ -626,7 +615,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
     const char* nxt = smemB + (buf ^ 1) * G_BUFB + frB;
     auto body = [&](auto req_tag) __attribute__((always_inline)) {
       constexpr bool REQ = decltype(req_tag)::value;       // request phase (loads for chunk c + 2), else transform + store phase (chunk c + 1)
-      if constexpr (REQ && !(DBG & 4)) {
+      if constexpr (REQ) {
         load_patch(c + 2);
         load_grad(c + 2);
       }
@@ -647,7 +636,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
         // staging of a wave's next chunk, balanced over its two phases: the request phase clamps + row-transforms the patch it asked
         // for at the top of this chunk in its last nine slots (after the barrier, when the loads have had ~13 slots), the store phase
         // column-transforms + stores it (and the gradient tile) in the slots before the barrier
-        if constexpr (REQ && !(DBG & 1)) {
+        if constexpr (REQ) {
           if constexpr (m >= 13 && m < 21) {
             affine_piece(2 * (m - 13));
             affine_piece(2 * (m - 13) + 1);
@@ -657,11 +646,11 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3_kernel(const IgemmParams
             row_piece(2 * (m - 21) + 1);
           }
         }
-        if constexpr (!REQ && !(DBG & 1)) {
+        if constexpr (!REQ) {
           if constexpr (m < 4) g_cols(buf ^ 1, m);
           if constexpr (m >= 4 && m < 12 && (m % 2) == 0) col_piece(buf ^ 1, (m - 4) / 2);
         }
-        if constexpr (m == 12 && !(DBG & 32)) __syncthreads();                   // all reads of `cur` are out (build 5's at slot 11), all stores into `nxt` are done (slot 10)
+        if constexpr (m == 12) __syncthreads();   // all reads of `cur` are out (build 5's at slot 11), all stores into `nxt` are done (slot 10)
         if constexpr (m == 14) issue_reads(6, cur, nxt);          // (its raw set is build 4's until that build's last part)
         __builtin_amdgcn_sched_barrier(0);
       });
@@ -706,8 +695,7 @@ constexpr int W_VOPB = 8 * W_VPLANE;              // 16 KiB
 constexpr int W_BUFB = W_GOPB + W_VOPB;
 constexpr size_t kWgwLds = (size_t)2 * W_BUFB;    // 96 KiB
 
-template <bool HA, int DBG = 0>     // DBG (timing ablations, wrong results; DN_WINO_WG_DBG = 2000 + bits): 1 no fragment reads (the split runs on registers the compiler
-                                    // cannot see through), 2 no split arithmetic, 4 no staging (loads, clamp, transforms, stores), 8 no barrier
+template <bool HA>
 __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParams p) {
   extern __shared__ __align__(16) float smem[];
   char* smemB = reinterpret_cast<char*>(smem);
@@ -857,13 +845,8 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
   // builds of a chunk: id 0 = B(nn 1), 1 = A(h 1), 2 = A(h 2), 3 = A(h 3) read the current buffer; 4 = A(h 0), 5 = B(nn 0) of the next chunk read
   // the next buffer; raw register set = id & 3.
   // Every fragment read is issued in the second half of a chunk (after the barrier), away from the store-phase waves' 12 x 1 KB stores
-  // of the first half (measured: -1 %; the reads cost what they cost wherever they are issued, ablation 2001)
+  // of the first half (measured: -1 %; the reads cost what they cost wherever they are issued)
   auto issue_reads = [&](int id, const char* cur, const char* nxt) {
-    if constexpr (DBG & 1) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(raw[id & 3][ks]));
-      return;
-    }
     const bool isB = id == 0 || id == 5;
     const char* buf = id >= 4 ? nxt : cur;
     if (isB) {
@@ -884,10 +867,6 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
     float* x = raw[id & 3];
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
-      if constexpr (DBG & 2) {
-        Pk[level][hf] = __builtin_bit_cast(unsigned, x[2 * hf]) ^ (unsigned)level;
-        continue;
-      }
       const f32x2 v2 = f32x2{x[2 * hf], x[2 * hf + 1]};
       const bf16x2 pc = __builtin_convertvector(v2, bf16x2);
       Pk[level][hf] = __builtin_bit_cast(unsigned, pc);
@@ -948,7 +927,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
     const char* nxt = smemB + (buf ^ 1) * W_BUFB;
     auto body = [&](auto req_tag) __attribute__((always_inline)) {
       constexpr bool REQ = decltype(req_tag)::value;       // request phase (loads for chunk c + 2), else transform + store phase (chunk c + 1)
-      if constexpr (REQ && !(DBG & 4)) load_chunk(c + 2);
+      if constexpr (REQ) load_chunk(c + 2);
       __builtin_amdgcn_sched_barrier(0);
       static_for<24>([&](auto mc) __attribute__((always_inline)) {
         constexpr int m = decltype(mc)::value;
@@ -965,12 +944,10 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
         if constexpr (m == 19) issue_reads(3, nxt, nxt);
         if constexpr (m == 20) issue_reads(0, nxt, nxt);
         if constexpr (m == 23) issue_reads(1, nxt, nxt);
-        // ---- staging of the wave's next chunk
         // ---- staging of the wave's next chunk: the request phase clamps + row-transforms what it asked for at the top of this chunk in
         //      its second half, the store phase column-transforms + stores before the barrier.  (Measured: everything in the store phase
         //      +3 %; the clamp in the build-free slots 9-11 / 15-17 +-0.)
-        if constexpr (DBG & 4) {
-        } else if constexpr (REQ) {
+        if constexpr (REQ) {
           if constexpr (m >= 13 && m < 19) {
             affine_piece((2 * (m - 13)) / 4, (2 * (m - 13)) % 4);
             affine_piece((2 * (m - 13) + 1) / 4, (2 * (m - 13) + 1) % 4);
@@ -984,7 +961,7 @@ __global__ void __launch_bounds__(512, 1) wino_wgrad_x3w_kernel(const IgemmParam
           if constexpr (m == 8) col_piece(buf ^ 1, 0);
           if constexpr (m == 10) col_piece(buf ^ 1, 1);
         }
-        if constexpr (m == 12 && !(DBG & 8)) __syncthreads();      // all reads of `cur` are long out (previous chunk), all stores into `nxt` are done (slot 10)
+        if constexpr (m == 12) __syncthreads();   // all reads of `cur` are long out (previous chunk), all stores into `nxt` are done (slot 10)
         __builtin_amdgcn_sched_barrier(0);
       });
     };
@@ -1092,50 +1069,12 @@ int launch_wino_wgrad(IgemmParams& p, float* dw, hipStream_t stream) {
   p.OW = p.GW;
   p.mTW = fastdiv_magic((unsigned)p.TW);
   p.mTH = fastdiv_magic((unsigned)p.TH);
-  const int dbg = knobs().wino_wg_dbg;
-  const bool x3 = p.compute == DN_COMPUTE_F32X3 && (dbg == 0 || dbg >= 1000);
-  auto kernel = x3 ? (p.any_affine ? wino_wgrad_x3_kernel<true> : wino_wgrad_x3_kernel<false>)
-                   : (p.any_affine ? wino_wgrad_kernel<true, 0> : wino_wgrad_kernel<false, 0>);
-  if (x3) {
-    switch (dbg) {            // DN_WINO_WG_DBG = 1000 + bits: timing ablations of the three-piece variant
-      case 1001: kernel = wino_wgrad_x3_kernel<true, 1>; break;
-      case 1002: kernel = wino_wgrad_x3_kernel<true, 2>; break;
-      case 1004: kernel = wino_wgrad_x3_kernel<true, 4>; break;
-      case 1005: kernel = wino_wgrad_x3_kernel<true, 5>; break;
-      case 1008: kernel = wino_wgrad_x3_kernel<true, 8>; break;
-      case 1015: kernel = wino_wgrad_x3_kernel<true, 15>; break;
-      case 1016: kernel = wino_wgrad_x3_kernel<true, 16>; break;
-      case 1032: kernel = wino_wgrad_x3_kernel<true, 32>; break;
-      case 1024: kernel = wino_wgrad_x3_kernel<true, 24>; break;
-      default: break;
-    }
-  }
-  switch (dbg) {
-    case 2: kernel = wino_wgrad_kernel<true, 2>; break;
-    case 6: kernel = wino_wgrad_kernel<true, 6>; break;
-    case 22: kernel = wino_wgrad_kernel<true, 22>; break;
-    case 54: kernel = wino_wgrad_kernel<true, 54>; break;
-    case 118: kernel = wino_wgrad_kernel<true, 118>; break;
-    default: break;
-  }
+  const bool x3 = p.compute == DN_COMPUTE_F32X3;
   // 128 x 64 x 8-position blocks when the output channels allow it (DN_WINO_WGW=0 keeps the 64 x 64 x 16 kernel)
-  bool wide = x3 && dbg == 0 && (p.Ntot % 128) == 0 && knobs().wino_wgw != 0;
-  if (wide) kernel = p.any_affine ? wino_wgrad_x3w_kernel<true> : wino_wgrad_x3w_kernel<false>;
-  if (x3 && dbg >= 2000 && (p.Ntot % 128) == 0) {            // ablations of the wide block (tools/wgw_ablate.sh)
-    wide = true;
-    switch (dbg - 2000) {
-      case 1: kernel = wino_wgrad_x3w_kernel<true, 1>; break;
-      case 2: kernel = wino_wgrad_x3w_kernel<true, 2>; break;
-      case 3: kernel = wino_wgrad_x3w_kernel<true, 3>; break;
-      case 4: kernel = wino_wgrad_x3w_kernel<true, 4>; break;
-      case 5: kernel = wino_wgrad_x3w_kernel<true, 5>; break;
-      case 6: kernel = wino_wgrad_x3w_kernel<true, 6>; break;
-      case 7: kernel = wino_wgrad_x3w_kernel<true, 7>; break;
-      case 8: kernel = wino_wgrad_x3w_kernel<true, 8>; break;
-      case 15: kernel = wino_wgrad_x3w_kernel<true, 15>; break;
-      default: kernel = wino_wgrad_x3w_kernel<true>; break;
-    }
-  }
+  const bool wide = x3 && (p.Ntot % 128) == 0 && knobs().wino_wgw != 0;
+  auto kernel = wide ? (p.any_affine ? wino_wgrad_x3w_kernel<true> : wino_wgrad_x3w_kernel<false>)
+                : x3 ? (p.any_affine ? wino_wgrad_x3_kernel<true> : wino_wgrad_x3_kernel<false>)
+                     : (p.any_affine ? wino_wgrad_kernel<true> : wino_wgrad_kernel<false>);
   const size_t lds = wide ? kWgwLds : kWgLds;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) {
@@ -1145,9 +1084,10 @@ int launch_wino_wgrad(IgemmParams& p, float* dw, hipStream_t stream) {
   const int Ktot = wg_ktot(p);
   const int total = (p.Ntot / 64) * (Ktot / 64) * splits;          // (the wide kernel: Ntot / 128 x 2 position halves -- the same count)
   DN_LAUNCH(kernel, dim3((total + 7) / 8 * 8), dim3(512), lds, stream, p);
-  if (wide) set_last_kernel("dn::wino_wgrad_x3w_kernel<%s>", p.any_affine ? "true" : "false");
-  else if (x3) set_last_kernel("dn::wino_wgrad_x3_kernel<%s, 0>", p.any_affine ? "true" : "false");
-  else set_last_kernel("dn::wino_wgrad_kernel<%s, %d>", p.any_affine ? "true" : "false", (dbg == 2 || dbg == 6 || dbg == 22 || dbg == 54 || dbg == 118) ? dbg : 0);
+  const char* ha = p.any_affine ? "true" : "false";
+  if (wide) set_last_kernel("dn::wino_wgrad_x3w_kernel<%s>", ha);
+  else if (x3) set_last_kernel("dn::wino_wgrad_x3_kernel<%s>", ha);
+  else set_last_kernel("dn::wino_wgrad_kernel<%s>", ha);
   int rc = check_launch("wino_wgrad_kernel");
   if (rc != DN_OK) return rc;
   const long long slab = (long long)p.Ntot * Ktot;

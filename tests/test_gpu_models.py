@@ -774,8 +774,7 @@ def test_heads_emit_the_reciprocal_with_the_disparity():
         assert z2.data_ptr() != z1.data_ptr() and torch.equal(z2, 1.0 / d)
 
 
-# Every path-selection switch the library still reads (csrc/dn_internal.h::Knobs; the timing / ablation selectors DN_WINO_DBG, DN_WINO_WG_DBG,
-# DN_LDS3_DBG, DN_WINO_DBGPTR produce wrong results by design and DN_PACK_BLOCKS only sizes a grid) plus the engine's own: each one puts
+# Every path-selection switch the library still reads (csrc/dn_internal.h::Knobs; DN_PACK_BLOCKS only sizes a grid) plus the engine's own: each one puts
 # some layers of the network on another kernel family, and each is held to the network-level parity bar.
 _SWITCH_CASES = [("DN_NO_WINOGRAD", "1"), ("DN_NO_WINOGRAD_WGRAD", "1"), ("DN_NO_DIRECT", "1"), ("DN_NO_THIN", "1"), ("DN_NO_THIN_CONV", "1"),
                  ("DN_NO_LDS3", "1"), ("DN_NO_SPLITK", "1"), ("DN_NO_WINO_SPLITK", "1"), ("DN_NO_X3_SPLITK", "1"), ("DN_NO_WINO8_TAIL", "1"),
