@@ -64,7 +64,7 @@ struct Knobs {
   bool no_direct;                        // DN_NO_DIRECT: no one-channel head kernels
   bool no_thin, no_thin_conv;            // DN_NO_THIN / DN_NO_THIN_CONV: the thin full-resolution layers on the tiled kernels (tests compare the three forms)
   bool no_lds3;                          // DN_NO_LDS3: no LDS-resident family (dn_lds3*.hip, dn_stemk.hip, stem3)
-  bool no_splitk, no_wino_splitk, no_x3_splitk, no_wino8_tail;   // DN_NO_SPLITK / DN_NO_WINO_SPLITK / DN_NO_X3_SPLITK / DN_NO_WINO8_TAIL: K splits of small grids off
+  bool no_wino_splitk, no_x3_splitk, no_wino8_tail;   // DN_NO_WINO_SPLITK / DN_NO_X3_SPLITK / DN_NO_WINO8_TAIL: K splits of small grids off
   bool no_x3_direct, no_x3_wgrad;        // DN_NO_X3_DIRECT / DN_NO_X3_WGRAD: the fp32 matrix instruction in the direct forward family / tiled weight gradient
   bool no_tap_windows;                   // DN_NO_TAP_WINDOWS: > 32-tap weight gradients on the unscheduled kernel
   int wino_wgw;                          // DN_WINO_WGW: 0 = keep the 64 x 64 x 16-position weight-gradient block where 128 x 64 x 8 would run (bitwise test)
@@ -241,6 +241,17 @@ struct ConvFamily {
 };
 const ConvFamily* conv_route(const dn_conv_desc* d, const IgemmParams& p);   // never null: the last row takes every plan
 
+// dn_tiled.hip: the tiled implicit-GEMM forward / input-gradient kernels (every plan no other row takes) and the 3x3 first-layer stem
+bool stem_eligible(const dn_conv_desc* d, const IgemmParams& p);
+int launch_stem(const IgemmParams& p, hipStream_t stream);
+int launch_tiled_conv(const IgemmParams& p, hipStream_t stream);   // picks the kernel and the tile shape
+// dn_tiled_wgrad.hip: the tiled weight gradient behind kWgradFamilies, and the direct weight re-lay
+void choose_splits(IgemmParams* p);                             // pixel splits: sets p->splits, p->m_per_split
+size_t generic_wgrad_workspace_bytes(const IgemmParams& p);     // after choose_splits
+int generic_wgrad(const dn_conv_desc* fwd, IgemmParams& p, const float* dy, float* dw, void* workspace, size_t workspace_bytes, hipStream_t s);
+int launch_direct_pack(const IgemmParams& p, const float* w, float* wp, hipStream_t stream);
+int launch_direct_pack_many(const PackEntry* tab_dev, int n, hipStream_t stream);
+
 // dn_direct.hip: matrix-core-free kernels for the one-channel disparity heads
 bool head_fwd_eligible(const dn_conv_desc* d, const IgemmParams& p);
 int launch_head_fwd(const IgemmParams& p, hipStream_t stream);
@@ -260,7 +271,7 @@ void wino_prepare(IgemmParams& p);                   // arithmetic and tile fiel
 bool wino_folds_bn_finalize(const IgemmParams& p);   // the launch will finish the BatchNorm statistics / the BatchNorm-backward sums itself
 bool wino_folds_bn_sums(const IgemmParams& p);
 int wino_splitk_choice(const IgemmParams& p);
-size_t conv_x3_splitk_workspace_upper_bytes(const IgemmParams& p);   // dn_conv.hip: K split of the three-piece direct kernel, over the tile shapes launch_tiled_conv may pick
+size_t conv_x3_splitk_workspace_upper_bytes(const IgemmParams& p);   // dn_tiled.hip: K split of the three-piece direct kernel, over the tile shapes launch_tiled_conv may pick
 size_t wino_splitk_workspace_bytes(const IgemmParams& p);
 // dn_winograd_wgrad.hip: Winograd weight gradient of the same layers (operands and output channels multiples of 64)
 bool wino_wgrad_eligible(const dn_conv_desc* fwd, const IgemmParams& p);
@@ -284,7 +295,7 @@ int launch_lds3_wgrad(const dn_conv_desc* fwd, IgemmParams& p, float* dw, hipStr
 bool lds3k_wgrad_eligible(const dn_conv_desc* fwd, const IgemmParams& p);      // 96-channel form (iconv1), eight waves
 size_t lds3k_wgrad_workspace_bytes(const IgemmParams& p);
 int launch_lds3k_wgrad(const dn_conv_desc* fwd, IgemmParams& p, float* dw, hipStream_t stream);
-int launch_wgrad_reduce(const IgemmParams& p, float* dw, hipStream_t stream);   // dn_conv.hip: fixed-order sum of p.splits slabs of p.ws -> dw
+int launch_wgrad_reduce(const IgemmParams& p, float* dw, hipStream_t stream);   // dn_tiled_wgrad.hip: fixed-order sum of p.splits slabs of p.ws -> dw
 // dn_wgrad_x3.hip: the tiled weight gradient with three-piece arithmetic on the bf16 matrix cores (64 / 128-wide n tiles, float4 operands)
 bool wgrad_x3_eligible(const IgemmParams& p);
 int launch_wgrad_x3(const IgemmParams& p, hipStream_t stream);

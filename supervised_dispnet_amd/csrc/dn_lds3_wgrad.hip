@@ -10,7 +10,7 @@
 //     of one b128 + two b32 reads per piece;
 //   * the four waves of a block take different rows and keep D[co][ci] of all taps (10 or 8 accumulator tiles) in registers across ALL
 //     tiles the persistent block walks; they meet once, at the end, through LDS, and the block writes one slab of the split-sum
-//     workspace that wgrad_reduce_kernel (dn_conv.hip) folds in a fixed order -- deterministic.
+//     workspace that wgrad_reduce_kernel (dn_tiled_wgrad.hip) folds in a fixed order -- deterministic.
 // The 1-channel concat piece (nearest-x2 disparity) and the 3-channel image have their taps on the lanes (column n = tap, or tap * 3 + ci):
 // those fragments are gathered from small fp32 planes (8 ds_read_b32) and split in registers.
 #include <stdlib.h>

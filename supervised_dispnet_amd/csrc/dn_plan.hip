@@ -86,7 +86,6 @@ static void read_knobs(Knobs* k) {
   k->no_direct = on("DN_NO_DIRECT");
   k->no_thin = on("DN_NO_THIN");
   k->no_thin_conv = on("DN_NO_THIN_CONV");
-  k->no_splitk = on("DN_NO_SPLITK");
   k->wino_wgw = num("DN_WINO_WGW", 1);
   k->wino_min_tiles = num("DN_WINO_MIN_TILES", 192);
   k->no_x3_direct = on("DN_NO_X3_DIRECT");

@@ -1,4 +1,4 @@
-// Tiled weight gradient with fp32 products on the bf16 matrix cores (round 4; the three-piece form of igemm_wgrad_u32_kernel, dn_conv.hip).
+// Tiled weight gradient with fp32 products on the bf16 matrix cores (round 4; the three-piece form of igemm_wgrad_u32_kernel, dn_tiled_wgrad.hip).
 //   ws[split][n][k] = sum over the split's pixels of G[pixel][n] * X[pixel][k]      (G = dy, X = the gathered input; conv-transpose: swapped)
 // The contraction runs over PIXELS, so on v_mfma_f32_32x32x16_bf16 a lane must hold eight consecutive pixels of one channel, while NHWC
 // tensors hold the channels of one pixel together.  The transposition is done by the staging threads (as in dn_lds3_wgrad.hip): a thread
