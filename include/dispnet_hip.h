@@ -519,6 +519,18 @@ int dn_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, co
  * the backward pass): dn_adam_tick advances the counter and the derived values ONCE per optimizer step, then every range is a
  * dn_adam_step_dev with step = NULL (no tick; `derived` as the tick left it).  Element-wise arithmetic: the same result as one call. */
 int dn_adam_tick(const double* hyper, int32_t* step, float* derived, dn_stream_t stream);
+/* torch.optim.SGD with momentum (train.py:300-301; dampening 0, nesterov off) over the same arena, fp32:
+ *   gi = g*grad_scale; if (weight_decay != 0) gi += weight_decay*p; buf = momentum*buf + gi; p -= lr*buf.
+ * buf is the momentum buffer and starts as ZEROS: momentum*0 + gi is the gradient copy torch's first step makes, so there is no step
+ * counter.  momentum == 0 takes the same path.  p, g, buf: any 4-byte-aligned pointers, n >= 1; 16-byte accesses are used where the three
+ * share their offset within 16 bytes, and every element sees the same arithmetic whichever lane handles it. */
+int dn_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, double momentum, double weight_decay, double grad_scale,
+                dn_stream_t stream);
+/* The same update with hyper = {lr, momentum} as doubles on the DEVICE (narrowed to float as the host form narrows its arguments: the
+ * two agree bit for bit), so that a captured step follows a scheduler that writes hyper[0].  A range of the arena per call (a bucket
+ * at a time under the backward pass) needs nothing further: there is no per-step state besides buf. */
+int dn_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const double* hyper, double weight_decay, double grad_scale,
+                    dn_stream_t stream);
 int dn_fill(float* p, float value, int64_t n, dn_stream_t stream);
 /* dst[i] = src[i], n floats (the owned copy engine.seed_grad takes of a gradient autograd hands over; on the launch tape like every
  * other kernel of this library, which a framework-side copy would not be). */

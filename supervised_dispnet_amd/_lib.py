@@ -164,6 +164,8 @@ SIGNATURES = {
     "dn_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _d, _d, _d, _d, _d, _i32, _d, _vp]),
     "dn_adam_step_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _d, _d, _vp, _vp, _d, _vp]),
     "dn_adam_tick": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "dn_sgd_step": (C.c_int, [_vp, _vp, _vp, _i64, _d, _d, _d, _d, _vp]),
+    "dn_sgd_step_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _d, _d, _vp]),
     "dn_fill": (C.c_int, [_vp, _f, _i64, _vp]),
     "dn_copy": (C.c_int, [_vp, _vp, _i64, _vp]),
     "dn_tape_begin": (_vp, []),

@@ -5,7 +5,7 @@ reduce gradients to GPU0 every iteration.  Here every rank owns a replica and th
 the 79.5 MB gradient arena per step, issued as a few contiguous buckets in the order backward produces them (decoder
 first), each launched the moment its last gradient has been written -- so all but the last bucket overlap with the
 encoder backward.  RCCL runs on its own HIP stream; torch.distributed inserts the event fences against the compute
-stream.  The 1/world factor is folded into the Adam kernel.  BatchNorm statistics stay per-replica, exactly like the
+stream.  The 1/world factor is folded into the optimizer kernel.  BatchNorm statistics stay per-replica, exactly like the
 reference's DataParallel (no SyncBN).  Device-agnostic on purpose: the same code runs over gloo on CPU in the tests.
 """
 import os
@@ -168,7 +168,7 @@ class GradReducer(object):
                 self._bucket_of[id(p)] = bi
         self._pending = None
         self._handles = []
-        self.optimizer = None           # FusedAdam.overlap_backward(): ranges of the update are applied as the buckets complete
+        self.optimizer = None           # FusedAdam / FusedSGD.overlap_backward(): ranges of the update are applied as the buckets complete
         self._opt_stream = None
         self._applied = set()
         self._lagging = None
@@ -181,7 +181,7 @@ class GradReducer(object):
         self._handles = []
 
     def take_step_applied(self):
-        """True once per finished backward pass whose buckets were all updated (consumed by FusedAdam.step)."""
+        """True once per finished backward pass whose buckets were all updated (consumed by the fused optimizer's step())."""
         done, self._step_applied = self._step_applied, False
         return done
 

@@ -1,10 +1,12 @@
-"""Flat parameter arena + fused Adam (reference: torch.optim.Adam at train.py:303-305,520-522).
+"""Flat parameter arena + fused Adam and SGD (reference: torch.optim.Adam at train.py:303-305,520-522, torch.optim.SGD at train.py:300-301).
 
 ParamArena (device-agnostic, pure plumbing): re-points every hot parameter at a slice of ONE fp32 buffer and gives each a
 gradient view into a second one (`param._dn_grad_view`), ordered by the order gradients are PRODUCED in backward, so
 the data-parallel reducer can all-reduce contiguous buckets as soon as they are complete.
 FusedAdam (HIP): one `dn_adam_step` launch over the whole arena; numerics follow torch.optim.Adam (amsgrad off):
 lerp / addcmul updates, denom = sqrt(v)/sqrt(1-b2^t) + eps, step_size = lr/(1-b1^t); grad * (1/world) folded in.
+FusedSGD (HIP): the same surface over the same arena with one `dn_sgd_step` launch; numerics follow torch.optim.SGD with momentum
+(dampening 0, nesterov off): buf = momentum*buf + (g + wd*p), p -= lr*buf, the buffer starting as zeros.
 """
 import torch
 
@@ -44,7 +46,43 @@ class ParamArena(object):
                 p.grad = None
 
 
-class FusedAdam(object):
+class _ArenaOptimizer(object):
+    """What the fused optimizers share: the arena, stray-gradient bookkeeping and the per-bucket overlap contract."""
+    arena = None
+    _overlap = None           # overlap_backward(): the bucket watcher that applies ranges of the update as their gradients complete
+
+    @property
+    def params(self):
+        return self.arena.params
+
+    def zero_grad(self, set_to_none=True):
+        # arena gradients are fully overwritten by the engine every backward; only stray autograd grads need clearing
+        for p in self.arena.params:
+            p.grad = None
+
+    def overlap_backward(self, reducer):
+        """Apply the update a gradient bucket at a time, as soon as the bucket's gradients (and, under data parallelism, their
+        all-reduce) are complete, on a stream of its own under the rest of the backward pass (distributed.GradReducer drives it; with
+        one rank the reducer exchanges nothing and only watches the buckets).  Element-wise arithmetic: bit-identical to one update
+        of the whole arena.  What is left at step() is bookkeeping; the unoverlappable tail of a step shrinks from the whole
+        arena's 0.09 ms pass to the last ~1 MB bucket's.  Contract: exactly one backward pass per step(), through the engine (no
+        gradient accumulation, no stray autograd .grad on the arena's parameters)."""
+        self._overlap = reducer
+        if reducer is not None:
+            reducer.optimizer = self
+        return self
+
+    def _take_overlapped_step(self):
+        """step() under overlap_backward: every range was applied as its bucket completed (GradReducer.finish() has applied the
+        stragglers and joined the stream); check the contract."""
+        who = type(self).__name__
+        if not self._overlap.take_step_applied():
+            raise RuntimeError(who + ".overlap_backward: step() without a backward pass + GradReducer.finish() before it")
+        if any(p.grad is not None for p in self.arena.params):
+            raise RuntimeError(who + ".overlap_backward: a parameter received its gradient through autograd (.grad), not the engine")
+
+
+class FusedAdam(_ArenaOptimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, production_order=None):
         self.arena = params if isinstance(params, ParamArena) else ParamArena(list(params), production_order)
         engine.require_cuda(self.arena.flat_p, "parameters")
@@ -77,27 +115,6 @@ class FusedAdam(object):
             self._dev["hyper"][0:1].fill_(float(lr))
             self._dev["lr"] = float(lr)
 
-    @property
-    def params(self):
-        return self.arena.params
-
-    def zero_grad(self, set_to_none=True):
-        # arena gradients are fully overwritten by the engine every backward; only stray autograd grads need clearing
-        for p in self.arena.params:
-            p.grad = None
-
-    def overlap_backward(self, reducer):
-        """Apply the update a gradient bucket at a time, as soon as the bucket's gradients (and, under data parallelism, their
-        all-reduce) are complete, on a stream of its own under the rest of the backward pass (distributed.GradReducer drives it; with
-        one rank the reducer exchanges nothing and only watches the buckets).  Element-wise arithmetic: bit-identical to one update
-        of the whole arena.  What is left at step() is bookkeeping; the unoverlappable tail of a step shrinks from the whole
-        arena's 0.09 ms pass to the last ~1 MB bucket's.  Contract: exactly one backward pass per step(), through the engine (no
-        gradient accumulation, no stray autograd .grad on the arena's parameters)."""
-        self._overlap = reducer
-        if reducer is not None:
-            reducer.optimizer = self
-        return self
-
     @torch.no_grad()
     def apply_range(self, lo, hi, grad_scale=1.0, tick=True):
         """Adam update of arena elements [lo, hi) on the current stream (engine.stream_scope); `tick`: this is the first range of the
@@ -123,11 +140,7 @@ class FusedAdam(object):
     def step(self, grad_scale=1.0):
         a = self.arena
         if self._overlap is not None:
-            # every range was applied as its bucket completed (GradReducer.finish() has applied the stragglers and joined the stream)
-            if not self._overlap.take_step_applied():
-                raise RuntimeError("FusedAdam.overlap_backward: step() without a backward pass + GradReducer.finish() before it")
-            if any(p.grad is not None for p in a.params):
-                raise RuntimeError("FusedAdam.overlap_backward: a parameter received its gradient through autograd (.grad), not the engine")
+            self._take_overlapped_step()
             self.step_count += 1
             engine.bump_param_epoch()
             return
@@ -148,6 +161,10 @@ class FusedAdam(object):
                   self.weight_decay, self.step_count, float(grad_scale), engine._stream())
         engine.bump_param_epoch()
 
+    def tape_state(self):
+        """The device tensors a replay check must compare (graph.TapedStep.verify); needs capturable(True)."""
+        return [self.arena.flat_p, self.exp_avg, self.exp_avg_sq, self._dev["step"], self._dev["derived"]]
+
     def state_dict(self):
         if self._dev is not None:
             self.step_count = int(self._dev["step"].item())
@@ -160,3 +177,112 @@ class FusedAdam(object):
             self._dev["step"].fill_(self.step_count)
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+
+
+def flat_momentum_from_torch_sgd(sd, params, arena):
+    """A torch.optim.SGD state dict (what --sgd runs wrote before FusedSGD existed, and what the reference writes) as one flat
+    momentum buffer in `arena`'s layout, on the CPU.  state[i] belongs to params[i], the list the optimizer was constructed from (the
+    arena orders its slices by gradient production instead).  A parameter without an entry never had a gradient: zeros, like the
+    padding behind odd-sized slices.  Needs no GPU."""
+    params = list(params)
+    state, groups = sd["state"], sd.get("param_groups", [])
+    count = sum(len(g["params"]) for g in groups) if groups else len(params)
+    if count != len(params):
+        raise ValueError("torch.optim.SGD state for %d parameters, this optimizer was built from %d" % (count, len(params)))
+    offset = {id(p): o for p, o in zip(arena.params, arena.offsets)}
+    flat = torch.zeros(arena.numel, dtype=torch.float32)
+    for i, entry in state.items():
+        i = int(i)
+        if not 0 <= i < len(params):
+            raise ValueError("torch.optim.SGD state has an entry for parameter %d of %d" % (i, len(params)))
+        buf = entry.get("momentum_buffer")
+        o = offset.get(id(params[i]))
+        if buf is None or o is None:          # (momentum 0 leaves None; a frozen parameter is not in the arena)
+            continue
+        if tuple(buf.shape) != tuple(params[i].shape):
+            raise ValueError("torch.optim.SGD momentum_buffer of parameter %d has shape %s, the parameter %s"
+                             % (i, tuple(buf.shape), tuple(params[i].shape)))
+        flat[o:o + buf.numel()] = buf.detach().reshape(-1).to("cpu", torch.float32)
+    return flat
+
+
+class FusedSGD(_ArenaOptimizer):
+    """torch.optim.SGD with momentum (dampening 0, nesterov off) as one dn_sgd_step launch over the arena: FusedAdam's surface, so
+    distributed.GradReducer, graph.TapedStep / GraphedStep and train.py take either.  The momentum buffer starts as zeros, which is the
+    gradient copy torch's first step makes (momentum*0 + g), so there is no step counter: any range of the arena is one launch and
+    apply_range's `tick` has nothing to do."""
+
+    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, production_order=None):
+        if isinstance(params, ParamArena):
+            self.arena, self._listed = params, list(params.params)
+        else:
+            self._listed = list(params)       # construction order: the index of a torch.optim.SGD state dict
+            self.arena = ParamArena(self._listed, production_order)
+        engine.require_cuda(self.arena.flat_p, "parameters")
+        self.weight_decay = float(weight_decay)
+        self.momentum_buffer = torch.zeros_like(self.arena.flat_p)
+        self.param_groups = [{"params": self.arena.params, "lr": float(lr), "momentum": float(momentum), "weight_decay": self.weight_decay,
+                              "dampening": 0, "nesterov": False}]
+        self._dev = None          # capturable(): device-resident (lr, momentum) for a captured or taped step
+        self._overlap = None
+
+    def capturable(self, on=True):
+        """Keep (lr, momentum) on the DEVICE (dn_sgd_step_dev) so that a captured step follows a scheduler: set_lr() writes the value."""
+        if on and self._dev is None:
+            g = self.param_groups[0]
+            self._dev = {"hyper": torch.tensor([float(g["lr"]), float(g["momentum"])], dtype=torch.float64, device=self.arena.flat_p.device),
+                         "lr": float(g["lr"])}
+        elif not on:
+            self._dev = None
+        return self
+
+    def set_lr(self, lr):
+        self.param_groups[0]["lr"] = float(lr)
+        if self._dev is not None and self._dev["lr"] != float(lr):
+            self._dev["hyper"][0:1].fill_(float(lr))
+            self._dev["lr"] = float(lr)
+
+    @torch.no_grad()
+    def apply_range(self, lo, hi, grad_scale=1.0, tick=True):
+        """SGD update of arena elements [lo, hi) on the current stream (engine.stream_scope).  `tick` is FusedAdam's once-per-step
+        advance of its counter; SGD has no per-step state, so it is accepted and unused."""
+        a, g = self.arena, self.param_groups[0]
+        n = hi - lo
+        ptr = lambda t: t.data_ptr() + 4 * lo
+        if self._dev is not None:
+            if self._dev["lr"] != float(g["lr"]):
+                self.set_lr(g["lr"])
+            engine.hbm_call("dn::sgd_dev_kernel", n * 20, "dn_sgd_step_dev", ptr(a.flat_p), ptr(a.flat_g), ptr(self.momentum_buffer), n,
+                            self._dev["hyper"].data_ptr(), self.weight_decay, float(grad_scale), engine._stream())
+        else:
+            engine.hbm_call("dn::sgd_kernel", n * 20, "dn_sgd_step", ptr(a.flat_p), ptr(a.flat_g), ptr(self.momentum_buffer), n,
+                            float(g["lr"]), float(g["momentum"]), self.weight_decay, float(grad_scale), engine._stream())
+
+    @torch.no_grad()
+    def step(self, grad_scale=1.0):
+        if self._overlap is not None:
+            self._take_overlapped_step()
+        else:
+            self.arena.gather_stray_grads()
+            self.apply_range(0, self.arena.numel, grad_scale)
+        engine.bump_param_epoch()
+
+    def tape_state(self):
+        """The device tensors a replay check must compare (graph.TapedStep.verify)."""
+        return [self.arena.flat_p, self.momentum_buffer]
+
+    def state_dict(self):
+        return {"momentum_buffer": self.momentum_buffer.clone(),
+                "param_groups": [{k: v for k, v in self.param_groups[0].items() if k != "params"}]}
+
+    def load_state_dict(self, sd):
+        """This class's own form, or a torch.optim.SGD state dict over the parameter list this optimizer was constructed from."""
+        if "momentum_buffer" in sd:
+            flat = sd["momentum_buffer"]
+            if flat.numel() != self.arena.numel:
+                raise ValueError("momentum_buffer of %d elements, the arena has %d" % (flat.numel(), self.arena.numel))
+        elif "state" in sd:
+            flat = flat_momentum_from_torch_sgd(sd, self._listed, self.arena)
+        else:
+            raise ValueError("neither a FusedSGD nor a torch.optim.SGD state dict (keys: %s)" % sorted(sd))
+        self.momentum_buffer.copy_(flat.reshape(-1))

@@ -10,7 +10,7 @@ What differs from the reference, on purpose:
   * one process per GPU over RCCL instead of single-process nn.DataParallel: `-b` stays the GLOBAL batch, every rank takes
     its contiguous slice, gradients are summed by the bucketed all-reduce (distributed.GradReducer), BatchNorm statistics
     stay per replica exactly as under DataParallel;
-  * Adam runs as one fused kernel over a flat arena; the 123.6 M unused VGG-classifier parameters are not optimised;
+  * Adam and SGD (--sgd) run as one fused kernel over a flat arena; the 123.6 M unused VGG-classifier parameters are not optimised;
   * --unsupervised gets the 5-tuple loader the reference's branch needs (C-1); unknown selectors raise ValueError (C-12);
   * `--dataset nyu` reads the reference's NYU Depth v2 .npy layout and runs its augmentation chain on the GPU (supervised_dispnet_amd/nyu.py,
     always at the reference's 256x352 crop); it needs --with-gt and refuses --unsupervised and --shards;
@@ -90,7 +90,7 @@ def build_parser():
     p.add_argument("--img-width", type=int, default=416, help="synthetic image width")
     p.add_argument("--train-pose", action="store_true", help="also optimise PoseExpNet (the reference never does, appendix C-3)")
     p.add_argument("--tape", dest="tape", action="store_true", default=None,
-                   help="supervised per-sample / multi-scale losses with the fused Adam: record the launches of one training step and re-issue "
+                   help="supervised per-sample / multi-scale losses with a fused optimizer (not --diff-lr): record the launches of one training step and re-issue "
                         "them with one call per step (supervised_dispnet_amd.graph.TapedStep); the second batch checks the replay against "
                         "the eager step bit for bit, a mismatch falls back to eager launches with a message.  This is the DEFAULT wherever the "
                         "setting is eligible (at the reference's own -b4 the eager step is host-bound: 5.0 ms against 3.5 taped); an "
@@ -240,7 +240,7 @@ def main(argv=None):
     from supervised_dispnet_amd import data as D, engine
     from supervised_dispnet_amd.distributed import GradReducer
     from supervised_dispnet_amd.functional import reciprocal
-    from supervised_dispnet_amd.optim import FusedAdam
+    from supervised_dispnet_amd.optim import FusedAdam, FusedSGD
 
     if args.compute is not None:
         engine.set_compute(args.compute)
@@ -334,31 +334,33 @@ def main(argv=None):
     if args.train_pose:
         hot += [p for p in pose_exp_net.parameters() if p.requires_grad]
     reducer = None
-    plain_params = None          # torch.optim path (--sgd / --diff-lr): gradients live in p.grad and are exchanged per step
+    plain_params = None          # torch.optim path (--diff-lr): gradients live in p.grad and are exchanged per step
+    order = disp_net._grad_production_order() if hasattr(disp_net, "_grad_production_order") else None
     if args.diff_lr:
         if not hasattr(disp_net, "get_1x_lr_params"):
             # the reference's only network with these methods is models/DORN.py:222-236 (train.py:306-312 calls them unconditionally and
             # dies with AttributeError for every other --network); the full DORN model is outside SURVEY.md section 8
             raise SystemExit("--diff-lr needs a network with get_1x_lr_params() / get_10x_lr_params() (reference: models.DORN only)")
+        # (not on the arena: the two groups interleave in production order, so FusedSGD would need a per-slice learning-rate table)
         groups = [{"params": disp_net.get_1x_lr_params(), "lr": args.lr}, {"params": disp_net.get_10x_lr_params(), "lr": args.lr * 10}]
         optimizer = torch.optim.SGD(groups, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
-    elif args.sgd:
-        optimizer = torch.optim.SGD([{"params": hot, "lr": args.lr}], lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
-    if args.diff_lr or args.sgd:
         plain_params = [p for g in optimizer.param_groups for p in g["params"]]
+    elif args.sgd:
+        if rank == 0:
+            print("=> setting sgd solver")
+        optimizer = FusedSGD(hot, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, production_order=order)
     else:
         if rank == 0:
             print("=> setting adam solver")
-        order = disp_net._grad_production_order() if hasattr(disp_net, "_grad_production_order") else None
         optimizer = FusedAdam(hot, lr=args.lr, betas=(args.momentum, args.beta), weight_decay=args.weight_decay, production_order=order)
-        if world > 1:
-            reducer = GradReducer(optimizer.arena)
-            engine.GradSink.reducer = reducer
+    if plain_params is None and world > 1:
+        reducer = GradReducer(optimizer.arena)
+        engine.GradSink.reducer = reducer
     if weights is not None and "optimizer" in weights and not args.monodepth2:
         try:
             optimizer.load_state_dict(weights["optimizer"])
         except Exception as e:    # a reference checkpoint carries torch.optim.Adam state (incl. the unused classifier slots)
-            print("=> optimizer state not restored ({}); Adam moments start from zero".format(e))
+            print("=> optimizer state not restored ({}); {} from zero".format(e, optimizer_state_name(optimizer)))
 
     if rank == 0:
         with open(os.path.join(save_path, args.log_summary), "w") as f:
@@ -416,8 +418,26 @@ def _to_device_batch(batch, device, unsupervised):
     return tgt.to(device, non_blocking=True), None, None, None, gt.to(device, non_blocking=True)
 
 
+def optimizer_state_name(optimizer):
+    """What the "optimizer state not restored" message says starts over."""
+    if hasattr(optimizer, "exp_avg"):
+        return "Adam moments start"
+    return "the SGD momentum buffer starts"
+
+
+def tape_refusal(args, optimizer):
+    """Why this run's training step cannot go on a launch tape (None: it can), as far as the command line and the optimizer decide it."""
+    if args.unsupervised or args.loss == "DORN" or args.monodepth2:
+        return "only the supervised depth losses are taped"
+    if args.photo_loss_weight != 1 or args.mask_loss_weight != 0 or args.smooth_loss_weight != 0:
+        return "needs -p 1 -m 0 -s 0 (the weighted sum of loss terms is framework-side arithmetic)"
+    if not hasattr(optimizer, "arena"):
+        return "needs a fused optimizer (not --diff-lr)"
+    return None
+
+
 class TapedTrainer(object):
-    """--tape: the supervised training step (forward, 1/disp, loss, backward, gradient exchange, Adam) through a launch tape.
+    """--tape: the supervised training step (forward, 1/disp, loss, backward, gradient exchange, optimizer) through a launch tape.
     The first full-size batch is recorded (a real step); the second one is written into the tape's static input buffers and the replay
     is checked against the same step issued eagerly from the same state, bit for bit -- on a batch the tape has not seen, so work it
     missed would show up as stale data; only then are further batches replayed.  Batches of another shape (the last one of an epoch),
@@ -430,14 +450,8 @@ class TapedTrainer(object):
         self.ts = None
         self.state = "new"            # new -> recorded -> verified | off
         self.img = self.gt = None
-        why = None
-        if args.unsupervised or args.loss == "DORN" or args.monodepth2:
-            why = "only the supervised depth losses are taped"
-        elif args.photo_loss_weight != 1 or args.mask_loss_weight != 0 or args.smooth_loss_weight != 0:
-            why = "needs -p 1 -m 0 -s 0 (the weighted sum of loss terms is framework-side arithmetic)"
-        elif not hasattr(optimizer, "arena"):
-            why = "needs the fused Adam (not --sgd / --diff-lr)"
-        else:
+        why = tape_refusal(args, optimizer)
+        if why is None:
             from supervised_dispnet_amd.distributed import data_parallel_world
             if data_parallel_world() > 1 and (args.loss.startswith("Multi") or args.loss == "DORN"):
                 # decided up front: found out by a failed recording, the first batch's forward ran twice (BatchNorm
@@ -500,8 +514,7 @@ class TapedTrainer(object):
                     self._off("the recording failed on another rank")
                 return float(loss.item())
             if self.state == "recorded":
-                st = [self.opt.arena.flat_p, self.opt.exp_avg, self.opt.exp_avg_sq, self.opt._dev["step"], self.opt._dev["derived"]]
-                st += [b for b in self.net.buffers() if b.is_cuda]
+                st = self.opt.tape_state() + [b for b in self.net.buffers() if b.is_cuda]
                 same, worst = self.ts.verify(st)                   # (leaves the state one step further: this batch's eager step)
                 ok = self._agree(bool(same))
                 agreed = True
