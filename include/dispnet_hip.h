@@ -586,6 +586,51 @@ int dn_u8_normalize_flip(const uint8_t* src, const uint8_t* flip, int32_t B, int
 int dn_flip_w(const float* src, const uint8_t* flip, int32_t B, int32_t H, int32_t W, float* dst, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Random scale-and-crop of the shard loader (reference custom_transforms.py: RandomScaleCrop :73-113), fused with
+ * the flip and the normalisation above.  Equality with the host chain (data.Transform(scale_crop=True)) is the contract.
+ * Draws per sample, on the host, in the reference's Compose order: the flip draw first, as without the augmentation; then
+ * sx, sy = uniform(1, 1.15, 2) (x first); sh = int(H * sy), sw = int(W * sx) (fp64 product, truncated); oy = randint(sh - H + 1),
+ * ox = randint(sw - W + 1).  All images of a sample (target and references) and its depth share them.
+ * Image, per frame F (uint8 [H][W][3]; the reference sees the same integers as float32):
+ *   1. flip: F'[y][x] = F[y][W-1-x] if the sample is flipped;
+ *   2. byte-scale by the frame's own min / max over all three channels, the rule of dn_imresize_u8 below:
+ *      uint8(clip(fp32((fp32(a) - cmin) * fp32(255.0 / (cmax - cmin))) + 0.5f, 0, 255)), scale 1 for a constant frame.  ALWAYS applied,
+ *      also when sh == H and sw == W (the reference calls imresize unconditionally, on a float array); every frame has its own min / max;
+ *   3. horizontal pass at the crop columns X = ox + x: Pillow's 8-bit bilinear coefficients of the axis W -> sw at output index X are a
+ *      first input index and at most 3 fixed-point taps of 22 bits; out = clip8((2^21 + sum_i k_i * A[y][first + i]) >> 22), stored as
+ *      uint8.  Skipped when sw == W;
+ *   4. vertical pass at the crop rows Y = oy + y, the same on the uint8 result of step 3 for the axis H -> sh.  Skipped when sh == H;
+ *   5. img[c][y][x] = ((float)u8 / 255 - mean[c]) / std[c] in IEEE fp32, that order: bit-identical to dn_u8_normalize_flip of the uint8
+ *      result.
+ * Depth, fp32 [H][W], finite values: 1. flip; 2. gmax = max(D) in fp32; 3. the same byte-scale over the map's own min / max (fp32
+ * subtraction, scale = fp32(255.0 / (fp64(max) - fp64(min))); a sparse map has min 0, an all-zero map scale 1); 4. the same two passes on
+ * one channel; 5. out = fp32(fp64(u8) / 255.0 * fp64(gmax)).  This is the reference as written: it multiplies by the maximum only (the
+ * minimum is not added back) and the ground truth comes out quantised to 256 levels.
+ * Intrinsics (host, after the flip rule): row 0 times sx and row 1 times sy, each product in fp64 and rounded to fp32 once; then
+ * cx -= ox, cy -= oy, in fp64 and rounded once; the inverse as without the augmentation.
+ *
+ * dn_scale_crop_minmax writes DN_IMAGE_CHUNKS partial (min, max) pairs per image in one launch: minmax_u8 = int32[N * B][DN_IMAGE_CHUNKS][2]
+ * over the uint8 frames [N][B][H][W][3] (N images per sample: target, references) and minmax_depth = float[B][DN_IMAGE_CHUNKS][2] over the
+ * fp32 maps [B][H][W]; the two consumers below fold them.  frames or depth may be NULL (with its workspace).
+ * table = int32[B][W + H][4] on the device, built on the host per sample: rows [0, W) are the crop columns, rows [W, W + H) the crop rows,
+ * each {first input index, k0, k1, k2} with unused k = 0.  A skipped axis is written as the identity, {index, 1 << 22, 0, 0}, which the
+ * same arithmetic passes through exactly.  `first` counts in the FLIPPED frame; the kernels mirror the index when they load.
+ * scaled_hw_host = int32[B][2] {sh, sw} on the host and max_taps = the largest tap count of the rows: sh < H, sw < W or more than
+ * DN_SCALE_CROP_TAPS taps is DN_ERR_BAD_ARG and nothing is launched -- never a truncated filter (upscaling has support 1, so valid draws
+ * cannot need more).  The kernels clamp every table index into the window they staged: a foreign table gives wrong pixels, not a fault.
+ * dn_scale_crop_u8: one launch for all N * B frames -> out = fp32[N][B][3][H][W]; flip = uint8[B] or NULL; mean_host / std_host: 3 floats
+ * each on the host.  dn_scale_crop_depth: depth fp32[B][H][W] -> out = fp32[B][H][W] (out of place).  Any H, W.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DN_SCALE_CROP_TAPS 3
+int dn_scale_crop_minmax(const uint8_t* frames, const float* depth, int32_t N, int32_t B, int32_t H, int32_t W, int32_t* minmax_u8,
+                         float* minmax_depth, dn_stream_t stream);
+int dn_scale_crop_u8(const uint8_t* frames, const uint8_t* flip, int32_t N, int32_t B, int32_t H, int32_t W, const int32_t* minmax_u8,
+                     const int32_t* table, const int32_t* scaled_hw_host, int32_t max_taps, const float* mean_host, const float* std_host,
+                     float* out, dn_stream_t stream);
+int dn_scale_crop_depth(const float* depth, const uint8_t* flip, int32_t B, int32_t H, int32_t W, const float* minmax_depth,
+                        const int32_t* table, const int32_t* scaled_hw_host, int32_t max_taps, float* out, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * NYU Depth v2 input chain (reference datasets/nyu_depth_v2.py:76-110).  Training: raw = the stored samples [B,5,H0,W0] fp32 (RGB 0..255,
  * depth in metres, 0/1 mask); params = double[B][8] {flip, angle in degrees, crop row, crop column, zoom s >= 1, colour gain, 0, 0},
  * drawn on the host.  dn_nyu_prefilter writes minmax = float[B][DN_NYU_MINMAX_CHUNKS][2] partial (min, max) over all five channels and

@@ -183,6 +183,9 @@ SIGNATURES = {
     "dn_tape_free": (None, [_vp]),
     "dn_u8_normalize_flip": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "dn_flip_w": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "dn_scale_crop_minmax": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dn_scale_crop_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "dn_scale_crop_depth": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "dn_nyu_prefilter": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_nyu_train_resample": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dn_nyu_val_resize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

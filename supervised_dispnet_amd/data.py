@@ -27,21 +27,79 @@ def normalization(imagenet=False, monodepth2=False):
     return [0.5, 0.5, 0.5], [0.5, 0.5, 0.5]
 
 
-class Transform(object):
-    """flip (train only) -> CHW float /255 -> normalise, applied coherently to images, depth and intrinsics."""
+SCALE_CROP_MAX = 1.15     # custom_transforms.py:81: up to 15 % per axis
 
-    def __init__(self, mean, std, flip):
+
+def draw_scale_crop(rng, H, W):
+    """The draws of custom_transforms.RandomScaleCrop (:81-82, :104-105) from `rng` (numpy.random or a RandomState), in its order:
+    -> (sx, sy, sh, sw, oy, ox).  The scaled size is the fp64 product, truncated."""
+    sx, sy = rng.uniform(1, SCALE_CROP_MAX, 2)
+    sh, sw = int(H * sy), int(W * sx)
+    oy = rng.randint(sh - H + 1)
+    ox = rng.randint(sw - W + 1)
+    return float(sx), float(sy), sh, sw, int(oy), int(ox)
+
+
+def scale_crop_intrinsics(intrinsics, sx, sy, oy, ox):
+    """Rows 0 / 1 times sx / sy, then the principal point minus the crop offset: every step in fp64, rounded to fp32 once."""
+    k = np.array(intrinsics, dtype=np.float32)
+    k[0] = (k[0].astype(np.float64) * sx).astype(np.float32)
+    k[1] = (k[1].astype(np.float64) * sy).astype(np.float32)
+    k[0, 2] = np.float32(np.float64(k[0, 2]) - ox)
+    k[1, 2] = np.float32(np.float64(k[1, 2]) - oy)
+    return k
+
+
+def bytescale(a):
+    """scipy.misc.bytescale of a float32 array by its own min / max: uint8(clip(fp32((a - min) * fp32(255 / (max - min))) + 0.5, 0, 255)),
+    scale 1 for a constant array (DESIGN.md sections 11 and 14)."""
+    a = np.asarray(a, dtype=np.float32)
+    cmin, cmax = float(a.min()), float(a.max())
+    scale = np.float32(255.0 / (cmax - cmin) if cmax > cmin else 1.0)
+    t = (a - np.float32(cmin)) * scale + np.float32(0.5)
+    return np.clip(t, 0, 255).astype(np.uint8)
+
+
+def imresize_crop(a, sh, sw, oy, ox):
+    """scipy.misc.imresize(a, (sh, sw))[oy:oy + H, ox:ox + W] of a float32 [H, W, 3] frame or [H, W] map -> uint8: byte-scale, then
+    Pillow's 8-bit bilinear resize (a no-op for an axis that keeps its size), then the crop."""
+    from PIL import Image
+    H, W = a.shape[:2]
+    im = Image.fromarray(bytescale(a)).resize((sw, sh), Image.BILINEAR)
+    return np.array(im)[oy:oy + H, ox:ox + W]
+
+
+class Transform(object):
+    """flip (train only) -> [scale and crop (train only)] -> CHW float /255 -> normalise, applied coherently to images, depth and
+    intrinsics.  `scale_crop` is the reference's RandomScaleCrop (custom_transforms.py:73-113) in its Compose position, drawn from the
+    global numpy.random as the reference's workers do; it is the host statement of what dn_scale_crop_u8 / _depth compute."""
+
+    def __init__(self, mean, std, flip, scale_crop=False):
         self.mean = torch.tensor(mean, dtype=torch.float32).view(3, 1, 1)
         self.std = torch.tensor(std, dtype=torch.float32).view(3, 1, 1)
         self.flip = flip
+        self.scale_crop = scale_crop
 
     def __call__(self, images, gt_depth, intrinsics):
-        if self.flip and random.random() < 0.5:
+        flip = bool(self.flip and random.random() < 0.5)
+        crop = draw_scale_crop(np.random, *images[0].shape[:2]) if self.scale_crop else None
+        return self.apply(images, gt_depth, intrinsics, flip, crop)
+
+    def apply(self, images, gt_depth, intrinsics, flip, crop=None):
+        """The chain for given draws: flip (bool) and crop = (sx, sy, sh, sw, oy, ox) or None."""
+        if flip:
             images = [np.ascontiguousarray(np.fliplr(im)) for im in images]
             gt_depth = np.ascontiguousarray(np.fliplr(gt_depth))
             if intrinsics is not None:
                 intrinsics = np.copy(intrinsics)
                 intrinsics[0, 2] = images[0].shape[1] - intrinsics[0, 2]
+        if crop is not None:
+            sx, sy, sh, sw, oy, ox = crop
+            images = [imresize_crop(im, sh, sw, oy, ox) for im in images]
+            gmax = float(np.max(np.asarray(gt_depth, dtype=np.float32)))                      # the maximum only (:92-93)
+            gt_depth = (imresize_crop(gt_depth, sh, sw, oy, ox).astype(np.float64) / 255.0 * gmax).astype(np.float32)
+            if intrinsics is not None:
+                intrinsics = scale_crop_intrinsics(intrinsics, sx, sy, oy, ox)
         tensors = [(torch.from_numpy(np.transpose(im, (2, 0, 1))).float() / 255 - self.mean) / self.std for im in images]
         return tensors, torch.from_numpy(np.ascontiguousarray(gt_depth)).float(), intrinsics
 

@@ -62,6 +62,52 @@ def table_rows(n, O):
     return np.ascontiguousarray(np.concatenate([first[:, None], count[:, None], k], axis=1), dtype=np.int32)
 
 
+SCALE_CROP_TAPS = 3       # DN_SCALE_CROP_TAPS
+
+
+@functools.lru_cache(maxsize=None)
+def _scale_crop_axis(n, O):
+    """The int32 [O, 4] rows {first, k0, k1, k2} of one upscaled axis for dn_scale_crop_u8 / _depth (n inputs -> O >= n outputs), and
+    the largest tap count.  O == n is the skipped pass, written as the identity {index, 1 << 22, 0, 0}."""
+    if O < n:
+        raise ValueError("scale-and-crop never shrinks an axis: {} -> {}".format(n, O))
+    rows = np.zeros((O, 1 + SCALE_CROP_TAPS), dtype=np.int32)
+    if O == n:
+        rows[:, 0] = np.arange(n)
+        rows[:, 1] = 1 << PRECISION_BITS
+        rows.setflags(write=False)
+        return rows, 1
+    first, count, k = resize_coefficients(n, O)
+    taps = int(count.max())
+    if taps > SCALE_CROP_TAPS:                       # cannot happen: upscaling has support 1
+        raise ValueError("{} taps per output for the axis {} -> {}; the table rows hold {}".format(taps, n, O, SCALE_CROP_TAPS))
+    rows[:, 0] = first
+    rows[:, 1:1 + k.shape[1]] = k
+    rows.setflags(write=False)
+    return rows, taps
+
+
+def scale_crop_rows(n, O, o0):
+    """-> (int32 [n, 4], taps): the rows of outputs [o0, o0 + n) of the axis n -> O, i.e. of the crop window that starts at o0."""
+    rows, taps = _scale_crop_axis(int(n), int(O))
+    if not 0 <= o0 <= O - n:
+        raise ValueError("crop offset {} outside [0, {}]".format(o0, O - n))
+    return rows[o0:o0 + n], taps
+
+
+def scale_crop_table(H, W, draws, out=None):
+    """The per-sample table int32 [B, W + H, 4] of the draws [(sh, sw, oy, ox)]: the W crop columns, then the H crop rows.
+    -> (table, largest tap count).  `out`: a buffer to fill (the loader's pinned staging)."""
+    B = len(draws)
+    table = np.empty((B, W + H, 4), dtype=np.int32) if out is None else out
+    taps = 1
+    for b, (sh, sw, oy, ox) in enumerate(draws):
+        table[b, :W], tx = scale_crop_rows(W, sw, ox)
+        table[b, W:], ty = scale_crop_rows(H, sh, oy)
+        taps = max(taps, tx, ty)
+    return table, taps
+
+
 def check_frame(frame, name):
     a = np.asarray(frame)
     if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:

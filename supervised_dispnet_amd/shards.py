@@ -14,6 +14,11 @@ The values are bit-identical to the host chain (`data.Transform`): ((float)u8 / 
 (`rng.random() < 0.5`, one draw per sample).  The draws come from a PRIVATE `random.Random(seed + rank)` that `set_epoch` re-seeds
 (seed, rank, epoch), so the flips are reproducible from --seed whatever else the process does with the global `random` module; a
 caller that wants the JPEG loader's exact draws passes its own generator as `flip_rng` (tests do).
+
+`scale_crop=True` adds the reference's RandomScaleCrop behind the flip: per sample the producer thread draws the
+scales and the crop offset from a private `numpy.random.RandomState` seeded like the flip generator (`aug_rng` overrides it), builds the
+windowed Pillow coefficient rows, uploads them with the batch and adjusts the intrinsics; `dn_scale_crop_minmax`, `dn_scale_crop_u8` and
+`dn_scale_crop_depth` then take the place of `dn_u8_normalize_flip` / `dn_flip_w`, again bit-identical to `data.Transform(scale_crop=True)`.
 """
 import json
 import os
@@ -25,6 +30,8 @@ import numpy as np
 import torch
 
 from . import _lib, engine
+from .data import draw_scale_crop, scale_crop_intrinsics
+from .inference import IMAGE_CHUNKS, scale_crop_table
 
 
 def write_shards(root, out_dir, train=True, sequence_length=3, with_gt=False):
@@ -105,7 +112,7 @@ class ShardLoader(object):
     (data.RankSampler)."""
 
     def __init__(self, shards, batch_size, device, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), flip=True, shuffle=True, seed=0,
-                 rank=0, world=1, with_refs=False, drop_last=True, prefetch=2, flip_rng=None, percentage=1):
+                 rank=0, world=1, with_refs=False, drop_last=True, prefetch=2, flip_rng=None, percentage=1, scale_crop=False, aug_rng=None):
         from .data import RankSampler
         self.set = shards if isinstance(shards, ShardSet) else ShardSet(shards, percentage=percentage, seed=seed)
         self.device = torch.device(device)
@@ -121,6 +128,11 @@ class ShardLoader(object):
         self._own_rng = flip_rng is None
         self._seed, self._rank = int(seed or 0), int(rank)
         self.rng = flip_rng if flip_rng is not None else random.Random(self._flip_seed(0))
+        self.scale_crop = bool(scale_crop)
+        self._own_aug_rng = aug_rng is None
+        self.aug_rng = aug_rng
+        if self.scale_crop and aug_rng is None:
+            self.aug_rng = np.random.RandomState(self._aug_seed(0))
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.nimg = 1 + (len(self.set.samples[0][1]) if with_refs else 0)
         self._ring, self._slot = [], 0           # pinned staging buffers, reused round-robin once their copy has completed
@@ -133,6 +145,8 @@ class ShardLoader(object):
                 self._ring.append({"u8": torch.empty((self.nimg, self.B, H, W, 3), dtype=torch.uint8).pin_memory(),
                                    "gt": torch.empty((self.B, H, W), dtype=torch.float32).pin_memory(),
                                    "fl": torch.empty((self.B,), dtype=torch.uint8).pin_memory(), "ev": None})
+                if self.scale_crop:
+                    self._ring[-1]["tb"] = torch.empty((self.B, W + H, 4), dtype=torch.int32).pin_memory()
         slot = self._ring[self._slot]
         self._slot = (self._slot + 1) % n
         if slot["ev"] is not None:
@@ -142,10 +156,15 @@ class ShardLoader(object):
     def _flip_seed(self, epoch):
         return (self._seed * 1000003 + self._rank) * 1000003 + int(epoch)
 
+    def _aug_seed(self, epoch):
+        return self._flip_seed(epoch) % (1 << 32)          # RandomState takes 32 bits
+
     def set_epoch(self, epoch):
         self.sampler.set_epoch(epoch)
         if self._own_rng:
             self.rng = random.Random(self._flip_seed(epoch))
+        if self.scale_crop and self._own_aug_rng:
+            self.aug_rng = np.random.RandomState(self._aug_seed(epoch))
 
     def __len__(self):
         return len(self.sampler)
@@ -159,6 +178,7 @@ class ShardLoader(object):
         u8n, gtn, flips = u8.numpy(), gt.numpy(), fl.numpy()
         flips[:] = 0
         intr = np.empty((b, 3, 3), dtype=np.float32)
+        crops = []
         for j, si in enumerate(idxs):
             tgt, refs, scene = s.samples[si]
             u8n[0, j] = s.frames[tgt]
@@ -170,7 +190,16 @@ class ShardLoader(object):
             if self.flip and self.rng.random() < 0.5:               # custom_transforms.py:61: one draw per sample
                 flips[j] = 1
                 k[0, 2] = W - k[0, 2]                               # :67-68
+            if self.scale_crop:                                     # :81-82, :104-105: behind the flip, as Compose orders them
+                sx, sy, sh, sw, oy, ox = draw_scale_crop(self.aug_rng, H, W)
+                crops.append((sh, sw, oy, ox))
+                k = scale_crop_intrinsics(k, sx, sy, oy, ox)
             intr[j] = k
+        aug = None
+        if self.scale_crop:
+            tb = slot["tb"][:b]
+            _, taps = scale_crop_table(H, W, crops, out=tb.numpy())
+            aug = (tb, np.ascontiguousarray([c[:2] for c in crops], dtype=np.int32), taps)
         with torch.cuda.stream(self.copy_stream):
             d_u8 = torch.empty(u8.shape, dtype=torch.uint8, device=self.device)
             d_gt = torch.empty(gt.shape, dtype=torch.float32, device=self.device)
@@ -182,13 +211,17 @@ class ShardLoader(object):
                     d_u8[i].copy_(u8[i], non_blocking=True)
             d_gt.copy_(gt, non_blocking=True)
             d_fl.copy_(fl, non_blocking=True)
+            if aug is not None:
+                d_tb = torch.empty(aug[0].shape, dtype=torch.int32, device=self.device)
+                d_tb.copy_(aug[0], non_blocking=True)
+                aug = (d_tb,) + aug[1:]
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         slot["ev"] = ev
-        return d_u8, d_gt, d_fl, intr, ev
+        return d_u8, d_gt, d_fl, intr, ev, aug
 
     def _finish(self, staged):
-        d_u8, d_gt, d_fl, intr, ev = staged
+        d_u8, d_gt, d_fl, intr, ev, aug = staged
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ev)
         for t in (d_u8, d_gt, d_fl):
@@ -196,15 +229,37 @@ class ShardLoader(object):
         n, b, H, W, _ = d_u8.shape
         imgs = torch.empty((n, b, 3, H, W), dtype=torch.float32, device=self.device)
         st = cur.cuda_stream
+        if aug is not None:
+            return self._batch(imgs, self._scale_crop(d_u8, d_gt, d_fl, aug, imgs, st), intr)
         for i in range(n):
             engine.hbm_call("dn::u8_norm_flip_vec_kernel", b * H * W * 15, "dn_u8_normalize_flip", d_u8[i].data_ptr(), d_fl.data_ptr(), b, H, W, 3,
                             self.mean_d.data_ptr(), self.std_d.data_ptr(), self.mean_h, self.std_h, imgs[i].data_ptr(), 3 * H * W, H * W, st)
         gt = torch.empty_like(d_gt)
         engine.hbm_call("dn::flip_w_kernel", b * H * W * 8, "dn_flip_w", d_gt.data_ptr(), d_fl.data_ptr(), b, H, W, gt.data_ptr(), st)
+        return self._batch(imgs, gt, intr)
+
+    def _batch(self, imgs, gt, intr):
         if not self.with_refs:
             return imgs[0], gt
         k = torch.from_numpy(intr)
-        return imgs[0], [imgs[i] for i in range(1, n)], k.to(self.device), torch.from_numpy(np.linalg.inv(intr)).to(self.device), gt
+        return imgs[0], [imgs[i] for i in range(1, imgs.shape[0])], k.to(self.device), torch.from_numpy(np.linalg.inv(intr)).to(self.device), gt
+
+    def _scale_crop(self, d_u8, d_gt, d_fl, aug, imgs, st):
+        """The three launches of the augmented path: partial min / max of every frame and map, all n * b frames, the depth -> gt."""
+        d_tb, scaled_hw, taps = aug
+        d_tb.record_stream(torch.cuda.current_stream(self.device))
+        n, b, H, W, _ = d_u8.shape
+        mm_u8 = torch.empty((n * b, IMAGE_CHUNKS, 2), dtype=torch.int32, device=self.device)
+        mm_gt = torch.empty((b, IMAGE_CHUNKS, 2), dtype=torch.float32, device=self.device)
+        gt = torch.empty_like(d_gt)
+        hw = scaled_hw.ctypes.data_as(_C.c_void_p)
+        engine.hbm_call("dn::scale_crop_minmax_kernel", (3 * n + 4) * b * H * W, "dn_scale_crop_minmax", d_u8.data_ptr(), d_gt.data_ptr(), n, b,
+                        H, W, mm_u8.data_ptr(), mm_gt.data_ptr(), st)
+        engine.hbm_call("dn::scale_crop_tile_kernel<unsigned char, 3>", n * b * H * W * 15, "dn_scale_crop_u8", d_u8.data_ptr(), d_fl.data_ptr(),
+                        n, b, H, W, mm_u8.data_ptr(), d_tb.data_ptr(), hw, taps, self.mean_h, self.std_h, imgs.data_ptr(), st)
+        engine.hbm_call("dn::scale_crop_tile_kernel<float, 1>", b * H * W * 8, "dn_scale_crop_depth", d_gt.data_ptr(), d_fl.data_ptr(), b, H, W,
+                        mm_gt.data_ptr(), d_tb.data_ptr(), hw, taps, gt.data_ptr(), st)
+        return gt
 
     def __iter__(self):
         q = queue.Queue(maxsize=self.prefetch)

@@ -7,7 +7,11 @@
   train_resident   training step on one batch resident in HBM (what bench.py times)
   train_shards     the same training step fed by the ShardLoader
 
-usage: python tools/loader_bench.py [--frames 2048] [--batch 32] [--steps 40] [--workers 16]      (one JSON line)"""
+--scale-crop measures the random scale-and-crop augmentation instead and prints its own JSON line: ShardLoader
+img/s with and without the flag in the same run, the three kernels' time per batch (HIP events; 1 and 3 images per sample), and
+data.Transform(scale_crop=True) on one host core.
+
+usage: python tools/loader_bench.py [--frames 2048] [--batch 32] [--steps 40] [--workers 16] [--scale-crop]      (one JSON line)"""
 import argparse, json, os, pathlib, sys, tempfile, time
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
 import numpy as np
@@ -18,6 +22,7 @@ ap.add_argument("--frames", type=int, default=2048)
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--workers", type=int, default=16)
+ap.add_argument("--scale-crop", action="store_true")
 a = ap.parse_args()
 
 import bench
@@ -55,6 +60,65 @@ def rate(it, steps, per=B):
     torch.cuda.synchronize()
     return k * per / (time.perf_counter() - t0)
 
+
+def scale_crop_report(repeats=5, launches=50):
+    """The numbers of DESIGN.md section 14: loader rates (best of `repeats` passes), kernel times (median of `repeats` windows of `launches` launches)."""
+    import ctypes
+    from supervised_dispnet_amd import _lib, inference as I
+    steps = min(a.steps * 2, len(st) // B)
+    for key, flag in (("loader_scale_crop_img_s", True), ("loader_plain_img_s", False)):
+        ld = S.ShardLoader(st, B, dev, flip=True, shuffle=True, seed=0, scale_crop=flag)
+        rate(ld, 5)
+        out[key] = max(rate(ld, steps) for _ in range(repeats))
+    rs = np.random.RandomState(1)
+    crops = [D.draw_scale_crop(rs, H, W)[2:] for _ in range(B)]
+    table, taps = I.scale_crop_table(H, W, crops)
+    hw = np.ascontiguousarray([c[:2] for c in crops], dtype=np.int32)
+    hwp = hw.ctypes.data_as(ctypes.c_void_p)
+    d_tb = torch.from_numpy(table).to(dev)
+    d_fl = torch.from_numpy((rs.rand(B) < 0.5).astype(np.uint8)).to(dev)
+    one = (ctypes.c_float * 3)(0.5, 0.5, 0.5)
+    stream = torch.cuda.current_stream().cuda_stream
+    for nimg in (1, 3):
+        u8 = torch.from_numpy(np.stack([np.asarray(st.frames[i * B:(i + 1) * B]) for i in range(nimg)])).to(dev)
+        gt = torch.from_numpy(np.array(st.depth[:B])).to(dev)
+        mm_u8 = torch.empty((nimg * B, 64, 2), dtype=torch.int32, device=dev)
+        mm_gt = torch.empty((B, 64, 2), dtype=torch.float32, device=dev)
+        img = torch.empty((nimg, B, 3, H, W), dtype=torch.float32, device=dev)
+        ogt = torch.empty_like(gt)
+        calls = {"minmax": lambda: _lib.call("dn_scale_crop_minmax", u8.data_ptr(), gt.data_ptr(), nimg, B, H, W, mm_u8.data_ptr(), mm_gt.data_ptr(), stream),
+                 "u8": lambda: _lib.call("dn_scale_crop_u8", u8.data_ptr(), d_fl.data_ptr(), nimg, B, H, W, mm_u8.data_ptr(), d_tb.data_ptr(), hwp, taps,
+                                         one, one, img.data_ptr(), stream),
+                 "depth": lambda: _lib.call("dn_scale_crop_depth", gt.data_ptr(), d_fl.data_ptr(), B, H, W, mm_gt.data_ptr(), d_tb.data_ptr(), hwp, taps,
+                                            ogt.data_ptr(), stream)}
+        for name, fn in calls.items():
+            fn()
+            times = []
+            for _ in range(repeats):                                 # one event pair around `launches` back-to-back launches
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(launches):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times.append(e0.elapsed_time(e1) * 1e3 / launches)
+            out["kernel_us_%s_%dimg" % (name, nimg)] = float(np.median(times))
+    # the host chain on ONE core: this process, torch and the BLAS / OpenMP pools held to one thread
+    torch.set_num_threads(1)
+    t = D.Transform(*D.normalization(), flip=True, scale_crop=True)
+    k = np.eye(3, dtype=np.float32)
+    m = 64
+    t0 = time.perf_counter()
+    for i in range(m):
+        t([np.asarray(st.frames[i]).astype(np.float32)], np.asarray(st.depth[i]), k)
+    out["host_chain_scale_crop_one_core_img_s"] = m / (time.perf_counter() - t0)
+    out["repeats"], out["launches_per_kernel"] = repeats, launches
+    print(json.dumps(out))
+
+
+if a.scale_crop:
+    scale_crop_report()
+    sys.exit(0)
 
 loader = S.ShardLoader(st, B, dev, flip=True, shuffle=True, seed=0)
 rate(loader, 5)

@@ -14,6 +14,8 @@ What differs from the reference, on purpose:
   * --unsupervised gets the 5-tuple loader the reference's branch needs (C-1); unknown selectors raise ValueError (C-12);
   * `--dataset nyu` reads the reference's NYU Depth v2 .npy layout and runs its augmentation chain on the GPU (supervised_dispnet_amd/nyu.py,
     always at the reference's 256x352 crop); it needs --with-gt and refuses --unsupervised and --shards;
+  * `--scale-crop` (off by default) adds the reference's RandomScaleCrop to the training samples, on the GPU with --shards
+    (DESIGN.md section 14) and in the loader workers otherwise; --dataset nyu and --synthetic refuse it;
   * `--synthetic N` (extension) trains on N synthetic samples with the statistics of SURVEY.md section 8d, for boxes
     without a dataset; tensorboard / progress-bar logging is replaced by plain prints and the two CSV logs.
 """
@@ -86,6 +88,10 @@ def build_parser():
     p.add_argument("--shards", default=None, metavar="SHARD_DIR",
                    help="training samples from pre-decoded uint8 shards (tools/make_shards.py DIR SHARD_DIR): flip / /255 / normalise run "
                         "on the GPU (dn_u8_normalize_flip), bit-identical to the JPEG loader's host chain")
+    p.add_argument("--scale-crop", action="store_true",
+                   help="train with the reference's RandomScaleCrop behind the flip (custom_transforms.py:73-113: zoom up to 15 %% per axis "
+                        "with scipy.misc.imresize, crop back, depth and intrinsics follow); on the GPU with --shards "
+                        "(dn_scale_crop_u8 / dn_scale_crop_depth), in the workers otherwise.  Never applied to validation")
     p.add_argument("--img-height", type=int, default=128, help="synthetic image height")
     p.add_argument("--img-width", type=int, default=416, help="synthetic image width")
     p.add_argument("--train-pose", action="store_true", help="also optimise PoseExpNet (the reference never does, appendix C-3)")
@@ -201,6 +207,10 @@ class Meter(object):
 
 def check_dataset_args(args):
     """Settings the NYU Depth v2 loader cannot serve, refused before anything touches the GPU (one line each)."""
+    if args.scale_crop and args.synthetic > 0:
+        raise SystemExit("--scale-crop augments decoded frames (scene folders or --shards); --synthetic samples are generated normalised")
+    if args.scale_crop and args.dataset == "nyu":
+        raise SystemExit("--scale-crop is the KITTI / scene-folder augmentation; --dataset nyu runs its own chain (rotate, zoom, colour)")
     if args.dataset != "nyu" or args.synthetic > 0:
         return
     if args.shards:
@@ -269,7 +279,8 @@ def main(argv=None):
         if args.shards:
             train_set = None                         # --shards replaces the JPEG train set: do not crawl the scene folders for it
         else:
-            train_set = D.SequenceFolder(args.data, transform=D.Transform(mean, std, flip=True), seed=args.seed, train=True,
+            train_set = D.SequenceFolder(args.data, transform=D.Transform(mean, std, flip=True, scale_crop=args.scale_crop), seed=args.seed,
+                                         train=True,
                                          sequence_length=args.sequence_length, percentage=args.data_amount, with_refs=with_refs)
         if args.with_gt:
             val_set = D.ValidationSet(args.data, transform=D.Transform(mean, std, flip=False))
@@ -296,7 +307,7 @@ def main(argv=None):
         from supervised_dispnet_amd.shards import ShardLoader
         mean, std = D.normalization(args.imagenet_normalization, args.monodepth2)
         train_loader = ShardLoader(args.shards, per_rank, device, mean=mean, std=std, flip=True, shuffle=True, seed=args.seed, rank=rank,
-                                   world=world, with_refs=with_refs, percentage=args.data_amount)
+                                   world=world, with_refs=with_refs, percentage=args.data_amount, scale_crop=args.scale_crop)
         train_sampler = train_loader                 # set_epoch() reshuffles (and re-seeds the flip draws)
         if rank == 0:
             print("{} samples found in {} train scenes (shards)".format(len(train_loader.set), len(train_loader.set.scenes)))
