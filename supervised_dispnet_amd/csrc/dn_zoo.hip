@@ -1,14 +1,13 @@
 // Pointwise pieces of the FCRN / ASPP nets (reference models/FCRN.py, models/ASPP.py, models/res_aspp.py), gfx950 only:
-// batch statistics of a materialised tensor in the conv epilogues' partial layout, BatchNorm apply without ReLU, an element-wise
-// activation, and the one-channel bilinear resize of F.interpolate (either align_corners).  HBM / latency bound, deterministic
-// (gathers and fixed-order sums, no float atomics).
+// an element-wise activation, the four-phase bias add / bias gradient of the up-projection, and the one-channel bilinear resize of
+// F.interpolate (either align_corners).  HBM / latency bound, deterministic (gathers and fixed-order sums, no float atomics).
+// (Their BatchNorm pieces -- statistics of a materialised tensor, apply without ReLU -- are in dn_bn.hip.)
 #include "dn_device.h"
 
 namespace dn {
 
 namespace {
 constexpr int kZThreads = 256;
-constexpr int kTileRows = 128;             // = kBnTileRows of dn_pointwise.hip: the row tile dn_bn_finalize merges
 
 inline int zblocks(long long n) {
   long long b = (n + kZThreads - 1) / kZThreads;
@@ -17,58 +16,6 @@ inline int zblocks(long long n) {
   return (int)b;
 }
 }  // namespace
-
-// one block per (row tile, 64-channel group): thread (c, q) sums rows q, q+4, ... of its channel, the four partial sums meet in LDS;
-// second pass about the tile's own mean (the tile is re-read from L2)
-__global__ void __launch_bounds__(kZThreads) bn_stats_partial_kernel(const float* __restrict__ x, long long rows, int C, float* __restrict__ partial) {
-  __shared__ float red[4][64];
-  __shared__ float mean_s[64];
-  const int c = blockIdx.y * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
-  const long long r0 = (long long)blockIdx.x * kTileRows;
-  const long long left = rows - r0;
-  const int n = left < kTileRows ? (int)left : kTileRows;
-  float s = 0.f;
-  if (c < C)
-    for (int r = q; r < n; r += 4) s += x[(r0 + r) * C + c];
-  red[q][threadIdx.x & 63] = s;
-  __syncthreads();
-  float tot = 0.f;
-  if (q == 0) {
-    tot = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-    mean_s[threadIdx.x] = tot / (float)n;
-  }
-  __syncthreads();
-  const float mu = mean_s[threadIdx.x & 63];
-  float m2 = 0.f;
-  if (c < C)
-    for (int r = q; r < n; r += 4) {
-      const float d = x[(r0 + r) * C + c] - mu;
-      m2 += d * d;
-    }
-  __syncthreads();
-  red[q][threadIdx.x & 63] = m2;
-  __syncthreads();
-  if (q == 0 && c < C) {
-    float* dst = partial + ((long long)blockIdx.x * C + c) * 2;
-    dst[0] = tot;
-    dst[1] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-  }
-}
-
-__global__ void __launch_bounds__(kZThreads) bn_apply_kernel(const float* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift,
-                                                             long long rows, int C, float* __restrict__ out) {
-  const int G = C / 4;
-  const long long total = rows * G;
-  for (long long i = blockIdx.x * (long long)kZThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kZThreads) {
-    const int g = (int)(i % G);
-    const f32x4 v = *reinterpret_cast<const f32x4*>(y + i * 4);
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * g), sh = *reinterpret_cast<const f32x4*>(shift + 4 * g);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = v[e] * sc[e] + sh[e];
-    *reinterpret_cast<f32x4*>(out + i * 4) = o;
-  }
-}
 
 __global__ void __launch_bounds__(kZThreads) act_fwd_kernel(const float* __restrict__ x, long long n, int act, float p0, float p1, float* __restrict__ out) {
   for (long long i = blockIdx.x * (long long)kZThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kZThreads) {
@@ -223,23 +170,6 @@ __global__ void __launch_bounds__(kZThreads) resize_bilinear_bwd_kernel(const fl
 using namespace dn;
 
 extern "C" {
-
-int32_t dn_bn_stats_rows(int64_t rows) { return (int32_t)((rows + kTileRows - 1) / kTileRows); }
-
-int dn_bn_stats_partial(const float* x, int64_t rows, int32_t C, float* partial, dn_stream_t stream) {
-  DN_REQUIRE(x && partial && rows > 0 && C > 0, DN_ERR_BAD_ARG, "dn_bn_stats_partial: bad argument");
-  DN_REQUIRE((rows + kTileRows - 1) / kTileRows < 65536ll * 32768ll, DN_ERR_UNSUPPORTED, "dn_bn_stats_partial: too many rows");
-  DN_LAUNCH(bn_stats_partial_kernel, dim3((unsigned)((rows + kTileRows - 1) / kTileRows), (C + 63) / 64), dim3(kZThreads), 0, as_stream(stream), x,
-                     (long long)rows, C, partial);
-  return check_launch("bn_stats_partial_kernel");
-}
-
-int dn_bn_apply_fwd(const float* y, const float* scale, const float* shift, int64_t rows, int32_t C, float* out, dn_stream_t stream) {
-  DN_REQUIRE(y && scale && shift && out && rows > 0 && C > 0, DN_ERR_BAD_ARG, "dn_bn_apply_fwd: bad argument");
-  DN_REQUIRE(C % 4 == 0, DN_ERR_UNSUPPORTED, "dn_bn_apply_fwd: need C%%4==0");
-  DN_LAUNCH(bn_apply_kernel, dim3(zblocks(rows * (C / 4))), dim3(kZThreads), 0, as_stream(stream), y, scale, shift, (long long)rows, C, out);
-  return check_launch("bn_apply_kernel");
-}
 
 int dn_act_fwd(const float* x, int64_t n, int32_t act, float p0, float p1, float* out, dn_stream_t stream) {
   DN_REQUIRE(x && out && n > 0 && act >= DN_ACT_NONE && act <= DN_ACT_SIGMOID_AFFINE, DN_ERR_BAD_ARG, "dn_act_fwd: bad argument");

@@ -404,11 +404,20 @@ def require_cuda(t, what):
                            "CPU fallback" % (what, t.device))
 
 
+class BnSums:
+    """The two column sums of a BatchNorm backward (sum dz, sum dz * xhat) as the launch that took them left them: per-block rows
+    partial[rows][C][stride] with the pair at `offset`.  `final` = the (dgamma, dbeta) tensors when that launch already summed the rows
+    too (dn_conv_desc.bnb_dgamma / bnb_dbeta), else None."""
+    __slots__ = ("partial", "rows", "stride", "offset", "final")
+
+    def __init__(self, partial, rows, stride=2, offset=0, final=None):
+        self.partial, self.rows, self.stride, self.offset, self.final = partial, rows, stride, offset, final
+
+
 class Act:
     """An NHWC fp32 activation [N,H,W,C] plus what the engine needs to know about it."""
-    __slots__ = ("t", "N", "H", "W", "C", "scale", "shift", "mean", "invstd", "grad", "grad_is_dz", "partial",
-                 "partial_rows", "partial_stride", "partial_offset", "needs_grad", "strides", "no_relu", "planar", "pool_src", "sums_ready",
-                 "recip_t", "bn_owner", "sums_final", "seed_borrow", "grad_borrowed")
+    __slots__ = ("t", "N", "H", "W", "C", "scale", "shift", "mean", "invstd", "grad", "grad_is_dz", "bn_sums", "needs_grad", "strides",
+                 "no_relu", "planar", "pool_src", "recip_t", "bn_owner", "seed_borrow", "grad_borrowed")
 
     def __init__(self, t, N, H, W, C, strides=None, needs_grad=True):
         self.t = t
@@ -416,20 +425,18 @@ class Act:
         self.scale = self.shift = self.mean = self.invstd = None
         self.grad = None
         self.grad_is_dz = False
-        self.partial = None
-        self.partial_rows = 0
-        self.partial_stride, self.partial_offset = 2, 0
+        self.bn_sums = None             # BnSums.  Invariant: not None <=> it holds the two column sums of the dz that belongs to the current
+                                        # .grad (.grad itself when .grad_is_dz, else .grad under the pending ReLU's mask).  Set by whoever
+                                        # overwrites .grad and takes the sums alongside; cleared by grad_dest() when a second consumer adds
+                                        # to .grad, and by bn_backward() when it turns .grad into dL/dy
         self.no_relu = False            # pending BatchNorm affine WITHOUT ReLU (bottleneck bn3 / downsample BN): only
                                         # block_bn_add_relu may consume it
-        self.sums_ready = False         # .partial already holds the BatchNorm backward's column sums of .grad (taken in the epilogue of the
-                                        # input-gradient kernel that wrote .grad: conv_dgrad / dn_conv_desc.bnb_*)
         self.pool_src = None            # (dpooled, idx): the gradient arrives through a 2x2 max-pool and is expanded by the BatchNorm
                                         # backward itself (dn_bn_bwd_apply_pool); .grad is then only the destination buffer
         self.planar = False             # .t is [N,C,H,W] (a network OUTPUT the caller's API wants planar: ord_c1, decode_c)
         self.recip_t = None             # a one-channel disparity head's 1 / disp, written by the head kernel (dn_conv_desc.recip_out)
         self.bn_owner = None            # (BatchNorm2d, GradSink) of a pre-BatchNorm activation: where the input-gradient kernel of the layer
                                         # above may put d(gamma), d(beta) when it finishes the sums itself (dn_conv_desc.bnb_dgamma / bnb_dbeta)
-        self.sums_final = None          # (dgamma, dbeta) tensors that already hold the two BatchNorm-backward sums
         self.seed_borrow = False        # the producing block reads a seeded gradient WITHOUT writing it (block_conv_act: out-of-place
                                         # activation backward): seed_grad() may hand the framework's tensor over instead of a copy
         self.grad_borrowed = False      # .grad is the framework's tensor: read-only
@@ -456,6 +463,15 @@ class Act:
 
     def new_like(self):
         return torch.empty((self.N, self.H, self.W, self.C), dtype=torch.float32, device=self.t.device)
+
+    def grad_dest(self):
+        """(.grad, accumulate) for a block that contributes to this gradient: the first writer gets a fresh tensor to overwrite, later
+        ones add to what is there -- and sums taken by the first writer no longer describe the result."""
+        if self.grad is None:
+            self.grad = self.new_like()
+            return self.grad, False
+        self.bn_sums = None
+        return self.grad, True
 
 
 class Tape:
@@ -876,19 +892,14 @@ def conv_dgrad(layer, dy, N, OH, OW, pieces, in_hw):
             tmp = torch.empty((N, IH, IW, a.C), dtype=torch.float32, device=dy.device)
             _fill_result(d.out[i], tmp, a.C, IH, IW, False)
         else:
-            first = a.grad is None
-            if first:
-                a.grad = a.new_like()
-            else:
-                a.sums_ready = False    # a second consumer adds to this gradient: sums taken by the first writer no longer describe it
-                a.sums_final = None
-            _fill_result(d.out[i], a.grad, a.C, IH, IW, not first)
+            g, acc = a.grad_dest()
+            _fill_result(d.out[i], g, a.C, IH, IW, acc)
     d.w_packed = layer.packed(kind, d).data_ptr()
     d.bias = None
     d.act = ACT_NONE
     # BatchNorm backward of the layer below: when this call is the (first) writer of the gradient of a pre-BatchNorm activation with a
     # pending BN + ReLU, let its epilogue take the column sums (sum dz, sum dz * xhat) the BatchNorm backward needs -- one full read of
-    # the gradient and one launch less per layer (dn_conv_desc.bnb_*); bn_backward() skips its sums pass when .sums_ready
+    # the gradient and one launch less per layer (dn_conv_desc.bnb_*); bn_backward() skips its sums pass when it finds .bn_sums
     _splitk_workspace(d, dy.device)
     fuse = None
     if BN_SUMS_FUSION and len(targets) == 1 and not layer.transposed and not layer.reflect:
@@ -901,19 +912,15 @@ def conv_dgrad(layer, dy, N, OH, OW, pieces, in_hw):
             scratch = torch.empty((max(rows, 1), a.C, 2), dtype=torch.float32, device=dy.device)
             d.bnb_partial = scratch.data_ptr()
             if _lib.load().dn_conv_dgrad_fuses_bn_sums(C.byref(d)) == 1:
-                fuse = (a, scratch, rows, None)
+                fuse = BnSums(scratch, rows)
                 if FOLD_FINALIZE and a.bn_owner is not None and d.splitk_ws:
                     # ... and FINISH the two sums in the launch's last-arriving blocks: d(gamma), d(beta) of the BatchNorm below land where
                     # bn_backward() would have its own sums launch put them
                     obn, osink = a.bn_owner
-                    dg, db = osink.dest(obn.weight), osink.dest(obn.bias)
-                    if dg is None:
-                        dg = torch.empty(a.C, dtype=torch.float32, device=dy.device)
-                    if db is None:
-                        db = torch.empty(a.C, dtype=torch.float32, device=dy.device)
+                    dg, db = osink.dest_or_new(obn.weight), osink.dest_or_new(obn.bias)
                     d.bnb_dgamma, d.bnb_dbeta = dg.data_ptr(), db.data_ptr()
                     if _lib.load().dn_conv_dgrad_folds_bn_sums(C.byref(d)) == 1:
-                        fuse = (a, scratch, rows, (dg, db))
+                        fuse.final = (dg, db)
                     else:
                         d.bnb_dgamma = d.bnb_dbeta = None
             else:
@@ -924,10 +931,7 @@ def conv_dgrad(layer, dy, N, OH, OW, pieces, in_hw):
                 4 * (dy.numel() + sum(p.act.rows * p.act.C for p in targets))):
         _lib.call("dn_convT2d_dgrad" if layer.transposed else "dn_conv2d_dgrad", C.byref(d), _stream())
     if fuse is not None:
-        a, scratch, rows, final = fuse
-        a.partial, a.partial_rows, a.partial_stride, a.partial_offset = scratch, rows, 2, 0
-        a.sums_ready = True
-        a.sums_final = final
+        targets[0].act.bn_sums = fuse
     for p, tmp in post:
         a = p.act
         cur = tmp
@@ -936,18 +940,14 @@ def conv_dgrad(layer, dy, N, OH, OW, pieces, in_hw):
                 cur = torch.empty((N, IH, IW, a.C), dtype=torch.float32, device=dy.device)
                 _lib.call("dn_reflect_fold", tmp.data_ptr(), N, IH, IW, a.C, rp, cur.data_ptr(), 0, _stream())
             else:
-                first = a.grad is None
-                if first:
-                    a.grad = a.new_like()
-                _lib.call("dn_reflect_fold", tmp.data_ptr(), N, IH, IW, a.C, rp, a.grad.data_ptr(), 0 if first else 1, _stream())
+                g, acc = a.grad_dest()
+                _lib.call("dn_reflect_fold", tmp.data_ptr(), N, IH, IW, a.C, rp, g.data_ptr(), int(acc), _stream())
                 continue
-        first = a.grad is None
-        if first:
-            a.grad = a.new_like()
+        g, acc = a.grad_dest()
         if a.C == 1:
-            _lib.call("dn_upsample2x_nearest_bwd", cur.data_ptr(), N, a.H, a.W, a.grad.data_ptr(), 0 if first else 1, _stream())
+            _lib.call("dn_upsample2x_nearest_bwd", cur.data_ptr(), N, a.H, a.W, g.data_ptr(), int(acc), _stream())
         else:
-            _lib.call("dn_upsample2x_nearest_bwd_nhwc", cur.data_ptr(), N, a.H, a.W, a.C, a.grad.data_ptr(), 0 if first else 1, _stream())
+            _lib.call("dn_upsample2x_nearest_bwd_nhwc", cur.data_ptr(), N, a.H, a.W, a.C, g.data_ptr(), int(acc), _stream())
 
 
 def colsum(partial, rows, Cn, stride=1, offset=0, out=None):
@@ -988,6 +988,12 @@ class GradSink:
     def dest(param):
         """In-place destination registered by an optimizer arena (contiguous, parameter-shaped), or None."""
         return getattr(param, "_dn_grad_view", None)
+
+    @staticmethod
+    def dest_or_new(param):
+        """Where a kernel writes this parameter's gradient: the arena's slice when there is one (no copy launch), else a fresh tensor."""
+        dst = getattr(param, "_dn_grad_view", None)
+        return dst if dst is not None else torch.empty_like(param, memory_format=torch.contiguous_format)
 
     def put(self, param, g):
         dst = getattr(param, "_dn_grad_view", None)
@@ -1034,60 +1040,60 @@ class GradSink:
 
 def bn_backward(y, bn, sink, training):
     """BatchNorm backward of an activation stored pre-BN with the affine pending (block_conv_bn, block_upproject): y.grad holds
-    dL/d(relu(bn(y))) -- or dz with its column sums in y.partial when y.grad_is_dz -- and becomes dL/dy in place; d(gamma), d(beta) go
+    dL/d(relu(bn(y))) -- or dz with its column sums in y.bn_sums when y.grad_is_dz -- and becomes dL/dy in place; d(gamma), d(beta) go
     to the sink.  Returns the gradient tensor."""
     g, y_t, Cn, dev = y.grad, y.t, y.C, y.t.device
     if not training:
         raise NotImplementedError("backward through eval-mode BatchNorm (frozen statistics) is not implemented")
     relu_pending = not y.grad_is_dz           # g is dL/d(relu output): the mask is applied by the kernels below
-    final = None
-    if relu_pending and y.sums_ready and not BN_MATERIALIZE_DZ:
-        y.sums_ready = False                  # the column sums came out of the epilogue of the kernel that wrote g (conv_dgrad)
-        final, y.sums_final = y.sums_final, None      # ... already summed over the blocks too (dgamma, dbeta): no sums launch at all
-    elif relu_pending:
-        y.sums_ready = False
-        if y.no_relu:
+    sums = y.bn_sums
+    if relu_pending and (sums is None or BN_MATERIALIZE_DZ):      # (sums from the epilogue of the kernel that wrote g, conv_dgrad, are
+        if y.no_relu:                                             #  ignored by the two-pass reference form: it takes its own)
             raise RuntimeError("a ReLU-less BatchNorm output must be consumed by block_bn_add_relu / block_bn_plain")
         nblk = _lib.load().dn_reduce_blocks(y.rows, Cn)
-        y.partial = torch.empty((nblk, Cn, 2), dtype=torch.float32, device=dev)
-        y.partial_rows = nblk
+        sums = BnSums(torch.empty((nblk, Cn, 2), dtype=torch.float32, device=dev), nblk)
         if BN_MATERIALIZE_DZ:
             hbm_call("dn::colreduce_kernel<dn::BnReluBwdOp, 4>", y.rows * Cn * 12, "dn_bn_relu_bwd_reduce", g.data_ptr(),
                      y_t.data_ptr(), y.scale.data_ptr(), y.shift.data_ptr(), y.mean.data_ptr(), y.invstd.data_ptr(), y.rows, Cn,
-                     y.partial.data_ptr(), _stream())
+                     sums.partial.data_ptr(), _stream())
         else:                                 # sums only: the apply pass re-derives the mask from y (one full-size write less)
             hbm_call("dn::colreduce_kernel<dn::BnReluBwdOp, 4>", y.rows * Cn * 8, "dn_bn_relu_bwd_sums", g.data_ptr(),
                      y_t.data_ptr(), y.scale.data_ptr(), y.shift.data_ptr(), y.mean.data_ptr(), y.invstd.data_ptr(), y.rows, Cn,
-                     y.partial.data_ptr(), _stream())
-    # written straight into the optimizer arena's gradient slices when there is one (no copy launches)
-    if final is not None:
-        dgamma, dbeta = final
-    else:
-        dgamma = sink.dest(bn.weight)
-        dbeta = sink.dest(bn.bias)
-        if dgamma is None:
-            dgamma = torch.empty(Cn, dtype=torch.float32, device=dev)
-        if dbeta is None:
-            dbeta = torch.empty(Cn, dtype=torch.float32, device=dev)
+                     sums.partial.data_ptr(), _stream())
+    elif sums is None:
+        raise RuntimeError("bn_backward: the column sums of this dz are gone (a second consumer added to the gradient after they were taken)")
+    # written straight into the optimizer arena's gradient slices when there is one (no copy launches); sums.final: already summed over
+    # the blocks too, by the launch that took them -- no sums launch at all
+    dgamma, dbeta = sums.final if sums.final is not None else (sink.dest_or_new(bn.weight), sink.dest_or_new(bn.bias))
     if y.pool_src is not None:                # gradient through the 2x2 max-pool: expanded here, never materialised as dz
         dpooled, pidx = y.pool_src
         hbm_call("dn::bn_bwd_apply_pool_kernel", y.rows * Cn * 8 + y.rows * Cn * 5 // 4, "dn_bn_bwd_apply_pool", dpooled.data_ptr(),
-                 pidx.data_ptr(), y_t.data_ptr(), y.mean.data_ptr(), y.invstd.data_ptr(), bn.weight.data_ptr(), y.partial.data_ptr(),
-                 y.partial_rows, y.partial_stride, y.partial_offset, y.N, y.H, y.W, Cn, g.data_ptr(), dgamma.data_ptr(),
+                 pidx.data_ptr(), y_t.data_ptr(), y.mean.data_ptr(), y.invstd.data_ptr(), bn.weight.data_ptr(), sums.partial.data_ptr(),
+                 sums.rows, sums.stride, sums.offset, y.N, y.H, y.W, Cn, g.data_ptr(), dgamma.data_ptr(),
                  dbeta.data_ptr(), _stream())
         y.pool_src = None
     elif relu_pending and not BN_MATERIALIZE_DZ:
         hbm_call(None, y.rows * Cn * 12, "dn_bn_bwd_apply_relu", g.data_ptr(), y_t.data_ptr(),
                  y.scale.data_ptr(), y.shift.data_ptr(), y.mean.data_ptr(), y.invstd.data_ptr(), bn.weight.data_ptr(),
-                 None if final is not None else y.partial.data_ptr(), y.partial_rows, y.partial_stride, y.partial_offset, y.rows, Cn,
+                 None if sums.final is not None else sums.partial.data_ptr(), sums.rows, sums.stride, sums.offset, y.rows, Cn,
                  dgamma.data_ptr(), dbeta.data_ptr(), _stream())
     else:
         hbm_call(None, y.rows * Cn * 12, "dn_bn_bwd_apply", g.data_ptr(), y_t.data_ptr(), y.mean.data_ptr(),
-                 y.invstd.data_ptr(), bn.weight.data_ptr(), y.partial.data_ptr(), y.partial_rows, y.partial_stride,
-                 y.partial_offset, y.rows, Cn, dgamma.data_ptr(), dbeta.data_ptr(), _stream())
+                 y.invstd.data_ptr(), bn.weight.data_ptr(), sums.partial.data_ptr(), sums.rows, sums.stride,
+                 sums.offset, y.rows, Cn, dgamma.data_ptr(), dbeta.data_ptr(), _stream())
+    y.bn_sums = None                          # g is dL/dy now
     sink.put(bn.weight, dgamma)
     sink.put(bn.bias, dbeta)
     return g
+
+
+def _bn_finalize(bn, partial, prow, count, conv_bias, mean, invstd, scale, shift, nbt):
+    """dn_bn_finalize: the batch statistics in `partial` (prow rows over `count` pixels; the conv bias shifts the mean only) become mean,
+    invstd and the (scale, shift) of bn's affine; bn's running buffers move.  `nbt`: _nbt_ptr(bn), taken ONCE per forward by the caller."""
+    _lib.call("dn_bn_finalize", partial.data_ptr(), prow, scale.numel(), count, _ptr(conv_bias.detach()) if conv_bias is not None else None,
+              bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+              bn.momentum if bn.momentum is not None else BN_MOMENTUM, bn.eps, mean.data_ptr(), invstd.data_ptr(),
+              scale.data_ptr(), shift.data_ptr(), nbt, _stream())
 
 
 def _bn_pending(y, bn, partial, prow, training, conv_bias=None):
@@ -1099,10 +1105,7 @@ def _bn_pending(y, bn, partial, prow, training, conv_bias=None):
     if training:
         y.mean = torch.empty(Cn, dtype=torch.float32, device=dev)
         y.invstd = torch.empty(Cn, dtype=torch.float32, device=dev)
-        _lib.call("dn_bn_finalize", partial.data_ptr(), prow, Cn, y.rows, _ptr(conv_bias.detach()) if conv_bias is not None else None,
-                  bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                  bn.momentum if bn.momentum is not None else BN_MOMENTUM, bn.eps, y.mean.data_ptr(), y.invstd.data_ptr(),
-                  y.scale.data_ptr(), y.shift.data_ptr(), _nbt_ptr(bn), _stream())
+        _bn_finalize(bn, partial, prow, y.rows, conv_bias, y.mean, y.invstd, y.scale, y.shift, _nbt_ptr(bn))
     else:
         _lib.call("dn_bn_eval_affine", Cn, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
                   bn.running_var.data_ptr(), bn.eps, y.scale.data_ptr(), y.shift.data_ptr(), _stream())
@@ -1132,10 +1135,7 @@ def block_conv_bn(tape, sink, x_piece, layer, bn, training, relu=True):
     y.bn_owner = (bn, sink)
     if training:
         if fold[0] is not True:              # (True: the convolution's last-arriving blocks finished the statistics themselves)
-            _lib.call("dn_bn_finalize", partial.data_ptr(), prow, Cn, y.rows, _ptr(layer.m.bias.detach()) if layer.m.bias is not None else None,
-                      bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                      bn.momentum if bn.momentum is not None else BN_MOMENTUM, bn.eps, y.mean.data_ptr(), y.invstd.data_ptr(),
-                      y.scale.data_ptr(), y.shift.data_ptr(), nbt, _stream())
+            _bn_finalize(bn, partial, prow, y.rows, layer.m.bias, mean, invstd, scale, shift, nbt)
     else:
         _lib.call("dn_bn_eval_affine", Cn, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
                   bn.running_var.data_ptr(), bn.eps, y.scale.data_ptr(), y.shift.data_ptr(), _stream())
@@ -1169,20 +1169,19 @@ def block_pool(tape, y):
         if p.grad is None:
             return
         nblk = _lib.load().dn_reduce_blocks(p.rows, y.C)
-        y.partial = torch.empty((nblk, y.C, 2), dtype=torch.float32, device=dev)
-        y.partial_rows = nblk
+        sums = y.bn_sums = BnSums(torch.empty((nblk, y.C, 2), dtype=torch.float32, device=dev), nblk)
         y.grad = y.new_like()
         y.grad_is_dz = True
         if BN_MATERIALIZE_DZ:
             hbm_call("dn::colreduce_kernel<dn::PoolBwdOp, 4>", y.rows * y.C * 4 * 2.25 + y.rows * y.C // 4, "dn_bn_relu_pool_bwd",
                      p.grad.data_ptr(), idx.data_ptr(), y.t.data_ptr(), y.mean.data_ptr(), y.invstd.data_ptr(), y.N, y.H, y.W, y.C,
-                     y.grad.data_ptr(), y.partial.data_ptr(), _stream())
+                     y.grad.data_ptr(), sums.partial.data_ptr(), _stream())
         else:
             # sums only; the BatchNorm backward of the producing layer (block_conv_bn) expands (dpooled, idx) into dy in ITS pass:
             # the full-resolution dz (three quarters zeros) is never written nor read back
             hbm_call("dn::colreduce_kernel<dn::PoolBwdOp, 4>", y.rows * y.C * 4 * 1.25 + y.rows * y.C // 4, "dn_bn_relu_pool_bwd_sums",
                      p.grad.data_ptr(), idx.data_ptr(), y.t.data_ptr(), y.mean.data_ptr(), y.invstd.data_ptr(), y.N, y.H, y.W, y.C,
-                     y.partial.data_ptr(), _stream())
+                     sums.partial.data_ptr(), _stream())
             y.pool_src = (p.grad, idx)
         p.grad = None
 
@@ -1206,12 +1205,8 @@ def block_conv_act(tape, sink, pieces, layer, act, p0=0.0, p1=0.0, out_hw=None, 
     if want_recip:
         y.recip_t = want_recip[0]             # depth = 1 / disp, written by the head kernel: functional.reciprocal() hands it out
     if stat_bn is not None:
-        Cn, dev = layer.Cout, y_t.device
-        scratch = torch.empty((4, Cn), dtype=torch.float32, device=dev)
-        _lib.call("dn_bn_finalize", partial.data_ptr(), prow, Cn, y.rows, _ptr(layer.m.bias.detach()) if layer.m.bias is not None else None,
-                  stat_bn.weight.data_ptr(), stat_bn.bias.data_ptr(), stat_bn.running_mean.data_ptr(), stat_bn.running_var.data_ptr(),
-                  stat_bn.momentum if stat_bn.momentum is not None else BN_MOMENTUM, stat_bn.eps, scratch[0].data_ptr(),
-                  scratch[1].data_ptr(), scratch[2].data_ptr(), scratch[3].data_ptr(), _nbt_ptr(stat_bn), _stream())
+        scratch = torch.empty((4, layer.Cout), dtype=torch.float32, device=y_t.device)
+        _bn_finalize(stat_bn, partial, prow, y.rows, layer.m.bias, *scratch, _nbt_ptr(stat_bn))
 
     def backward():
         if y.grad is None:                   # an output no loss term reads (autograd hands None): no gradient, as in the reference
@@ -1280,11 +1275,8 @@ def block_bilinear_up2(tape, d, out_hw):
     def backward():
         if up.grad is None:
             return
-        first = d.grad is None
-        if first:
-            d.grad = d.new_like()
-        _lib.call("dn_upsample2x_bilinear_bwd", up.grad.data_ptr(), d.N, d.H, d.W, OH, OW, d.grad.data_ptr(),
-                  0 if first else 1, _stream())
+        g, acc = d.grad_dest()
+        _lib.call("dn_upsample2x_bilinear_bwd", up.grad.data_ptr(), d.N, d.H, d.W, OH, OW, g.data_ptr(), int(acc), _stream())
         up.grad = None
 
     tape.push(backward)
@@ -1321,21 +1313,10 @@ def block_ord_head(tape, sink, x, conv, mask):
         g = o.grad if o.grad.is_contiguous() else o.grad.contiguous()
         nblk = _lib.load().dn_ord_head_bwd_blocks(N, H * W)
         ws = torch.empty(nblk * (2 * K * 16 + 2 * K), dtype=torch.float32, device=dev)
-        dw = sink.dest(conv.weight)
-        if dw is None:
-            dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
-        db = sink.dest(conv.bias)
-        if db is None:
-            db = torch.empty_like(conv.bias)
-        first = x.grad is None
-        if x.needs_grad:
-            if first:
-                x.grad = x.new_like()
-            dx = x.grad
-        else:
-            dx, first = x.new_like(), True
+        dw, db = sink.dest_or_new(conv.weight), sink.dest_or_new(conv.bias)
+        dx, acc = x.grad_dest() if x.needs_grad else (x.new_like(), False)
         hbm_call("dn::ord_head_bwd_kernel", px * (K + 48) * 4, "dn_ord_head_bwd", x.t.data_ptr(), mp, w.data_ptr(), b.data_ptr(), g.data_ptr(), N,
-                 H * W, K, dx.data_ptr(), 0 if first else 1, ws.data_ptr(), dw.data_ptr(), db.data_ptr(), _stream())
+                 H * W, K, dx.data_ptr(), int(acc), ws.data_ptr(), dw.data_ptr(), db.data_ptr(), _stream())
         sink.put(conv.bias, db)
         sink.put(conv.weight, dw)
         o.grad = None
@@ -1354,13 +1335,11 @@ def block_channel_scale(tape, x, mask):
     def backward():
         if out.grad is None:
             return
-        if x.grad is None:
-            x.grad = x.new_like()
-            _lib.call("dn_channel_scale", out.grad.data_ptr(), mask.data_ptr(), x.N, x.H * x.W, x.C, x.grad.data_ptr(), _stream())
-        else:
-            tmp = x.new_like()
-            _lib.call("dn_channel_scale", out.grad.data_ptr(), mask.data_ptr(), x.N, x.H * x.W, x.C, tmp.data_ptr(), _stream())
-            x.grad.add_(tmp)
+        g, acc = x.grad_dest()
+        dst = x.new_like() if acc else g          # (the kernel overwrites: a second consumer's share goes through a scratch tensor)
+        _lib.call("dn_channel_scale", out.grad.data_ptr(), mask.data_ptr(), x.N, x.H * x.W, x.C, dst.data_ptr(), _stream())
+        if acc:
+            g.add_(dst)
         out.grad = None
 
     tape.push(backward)
@@ -1392,21 +1371,17 @@ def block_bn_add_relu(tape, y, r):
         partial = torch.empty((nblk, y.C, 4), dtype=torch.float32, device=dev)
         y.grad = y.new_like()
         y.grad_is_dz = True
-        y.partial, y.partial_rows, y.partial_stride, y.partial_offset = partial, nblk, 4, 0
-        dr, acc = None, 0
+        y.bn_sums = BnSums(partial, nblk, 4, 0)
+        dr, acc = None, False
         if ds:
-            r.grad = r.new_like()
+            dr = r.grad = r.new_like()
             r.grad_is_dz = True
-            r.partial, r.partial_rows, r.partial_stride, r.partial_offset = partial, nblk, 4, 2
-            dr = r.grad
+            r.bn_sums = BnSums(partial, nblk, 4, 2)
         elif r is not None and r.needs_grad:
-            acc = 0 if r.grad is None else 1
-            if r.grad is None:
-                r.grad = r.new_like()
-            dr = r.grad
+            dr, acc = r.grad_dest()
         _lib.call("dn_bn_add_relu_bwd", out.grad.data_ptr(), out_t.data_ptr(), y.t.data_ptr(), y.mean.data_ptr(), y.invstd.data_ptr(),
                   r.t.data_ptr() if r is not None else None, r.mean.data_ptr() if ds else None, r.invstd.data_ptr() if ds else None, y.rows, y.C, y.grad.data_ptr(),
-                  _ptr(dr), acc, partial.data_ptr(), _stream())
+                  _ptr(dr), int(acc), partial.data_ptr(), _stream())
         out.grad = None
 
     tape.push(backward)
@@ -1435,10 +1410,8 @@ def block_maxpool3s2(tape, x, ceil_mode=False):
     def backward():
         if out.grad is None or not x.needs_grad:
             return
-        first = x.grad is None
-        if first:
-            x.grad = x.new_like()
-        _lib.call("dn_maxpool3s2_bwd", out.grad.data_ptr(), idx.data_ptr(), x.N, x.H, x.W, x.C, cm, x.grad.data_ptr(), 0 if first else 1, _stream())
+        g, acc = x.grad_dest()
+        _lib.call("dn_maxpool3s2_bwd", out.grad.data_ptr(), idx.data_ptr(), x.N, x.H, x.W, x.C, cm, g.data_ptr(), int(acc), _stream())
         out.grad = None
 
     tape.push(backward)
@@ -1462,11 +1435,9 @@ def block_maxpool2(tape, x):
     def backward():
         if out.grad is None or not x.needs_grad:
             return
-        first = x.grad is None
-        if first:
-            x.grad = x.new_like()
+        g, acc = x.grad_dest()
         hbm_call("dn::maxpool2_bwd_kernel", x.rows * x.C * 4 * 1.25 + x.rows * x.C // 4, "dn_maxpool2_bwd", out.grad.data_ptr(), idx.data_ptr(),
-                 x.N, x.H, x.W, x.C, x.grad.data_ptr(), 0 if first else 1, _stream())
+                 x.N, x.H, x.W, x.C, g.data_ptr(), int(acc), _stream())
         out.grad = None
 
     tape.push(backward)
@@ -1494,7 +1465,7 @@ def block_spatial_mean(tape, x, scale=1.0):
             return
         if x.grad is not None:
             raise RuntimeError("block_spatial_mean: single-consumer input expected")
-        x.grad = x.new_like()
+        x.grad, x.bn_sums = x.new_like(), None
         _lib.call("dn_spatial_mean_bwd", out.grad.data_ptr(), x.N, x.H * x.W, x.C, scale, x.grad.data_ptr(), _stream())
         out.grad = None
 
@@ -1520,12 +1491,11 @@ def block_bn_plain(tape, y):
             raise NotImplementedError("backward through eval-mode BatchNorm (frozen statistics) is not implemented")
         dev = y.t.device
         nblk = _lib.load().dn_reduce_blocks(y.rows, y.C)
-        y.partial = torch.empty((nblk, y.C, 2), dtype=torch.float32, device=dev)
-        y.partial_rows, y.partial_stride, y.partial_offset = nblk, 2, 0
+        sums = BnSums(torch.empty((nblk, y.C, 2), dtype=torch.float32, device=dev), nblk)
         zero, one = torch.zeros(y.C, dtype=torch.float32, device=dev), torch.ones(y.C, dtype=torch.float32, device=dev)
         _lib.call("dn_bn_relu_bwd_sums", out.grad.data_ptr(), y.t.data_ptr(), zero.data_ptr(), one.data_ptr(), y.mean.data_ptr(),
-                  y.invstd.data_ptr(), y.rows, y.C, y.partial.data_ptr(), _stream())
-        y.grad = out.grad
+                  y.invstd.data_ptr(), y.rows, y.C, sums.partial.data_ptr(), _stream())
+        y.grad, y.bn_sums = out.grad, sums
         y.grad_is_dz = True
         out.grad = None
 
@@ -1681,10 +1651,8 @@ def block_resize_bilinear(tape, d, out_hw, align_corners=True):
     def backward():
         if out.grad is None:
             return
-        first = d.grad is None
-        if first:
-            d.grad = d.new_like()
-        _lib.call("dn_resize_bilinear_bwd", out.grad.data_ptr(), d.N, d.H, d.W, OH, OW, ac, d.grad.data_ptr(), 0 if first else 1, _stream())
+        g, acc = d.grad_dest()
+        _lib.call("dn_resize_bilinear_bwd", out.grad.data_ptr(), d.N, d.H, d.W, OH, OW, ac, g.data_ptr(), int(acc), _stream())
         out.grad = None
 
     tape.push(backward)

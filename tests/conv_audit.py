@@ -529,7 +529,7 @@ class Audit(object):
         for p in pieces:
             a = p.act
             pre.append(a.grad[imgs].double().clone() if (a.needs_grad and a.grad is not None) else None)
-        partial_before = [p.act.partial for p in pieces]
+        sums_before = [p.act.bn_sums for p in pieces]
         orig(*args, **kwargs)
         torch.cuda.synchronize()
         kernel = self._kernel()
@@ -541,7 +541,7 @@ class Audit(object):
         c = bound(kernel, "dgrad")
         c0 = 0
         res = []
-        for p, before, pb in zip(pieces, pre, partial_before):
+        for p, before, sb in zip(pieces, pre, sums_before):
             a = p.act
             r, Ar = ref[..., c0:c0 + a.C], Aref[..., c0:c0 + a.C]
             c0 += a.C
@@ -554,8 +554,8 @@ class Audit(object):
                 got = got - before
                 Ar = Ar + before.abs()            # the accumulation's own rounding: one ulp of the sum
             res.append(compare(got, r, Ar, c))
-            if a.sums_ready and a.partial is not None and a.partial is not pb:
-                self._check_dgrad_bn_sums(name, kernel, a, a.partial, a.sums_final)
+            if a.bn_sums is not None and a.bn_sums is not sb:
+                self._check_dgrad_bn_sums(name, kernel, a, a.bn_sums.partial, a.bn_sums.final)
         ok = all(x[0] for x in res)
         self._row(name, "dgrad", kernel, "dx", ok, max(x[1] for x in res), max(x[2] for x in res), sum(x[3] for x in res), geo,
                   [(p.act.C, p.up, p.act.scale is not None, p.act.grad is not None) for p in pieces], c)

@@ -485,7 +485,7 @@ def test_config4_pointwise_passes_at_full_size_vs_pytorch_cpu():
         bad = (got - z_.grad).abs() > 1e-6
         assert bad.float().mean() < 1e-5
     # column sums produced alongside (dbeta, dgamma-precursor) against the CPU in fp64
-    part = ya.partial.double().sum(0)                                                       # [C][4]
+    part = ya.bn_sums.partial.double().sum(0)                                                      # [C][4]
     # the sums are over the dz the kernel itself wrote (checked element-wise above): a ReLU mask that flips where |z| is within
     # rounding of zero moves a column sum by one whole |go| <= 0.5, which is not a summation error
     dz = ya.grad.permute(0, 3, 1, 2).cpu().double()
