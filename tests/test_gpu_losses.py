@@ -6,7 +6,8 @@ Stated tolerances: scalar losses rtol 1e-5 (2e-5 where an exp/log chain is invol
 absolute floor relative to max|ref|; warped images atol 2e-5 (a bilinear gather of fp32 coordinates: coordinate round-off
 of ~1e-6 px times image gradient); pose gradients rtol 1e-3 (sums over all pixels); integer outputs exact.
 The fp64 comparison of the warp / photometric / SSIM / smoothness kernels, on inputs that fire their out-of-range, clamp and grid-stride
-branches and with a measured tolerance, is tests/test_gpu_geom_fp64.py (cases and checker: tests/geom_audit.py).
+branches and with a measured tolerance, is tests/test_gpu_geom_fp64.py (cases and checker: tests/geom_audit.py); that of the masked
+losses, the upsample, the explainability loss, the ordinal kernels, SID and compute_errors is tests/test_gpu_loss_fp64.py (tests/loss_audit.py).
 """
 import numpy as np
 import pytest
