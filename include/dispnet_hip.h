@@ -284,6 +284,34 @@ int dn_bn_bwd_apply_pool(const float* dpooled, const uint8_t* idx, const float* 
                          int32_t W, int32_t C, float* dy, float* dgamma, float* dbeta, dn_stream_t stream);
 int32_t dn_reduce_blocks(int64_t rows, int32_t C);   /* rows of `partial` the reduce kernels above write */
 
+/* ---- backward of a FROZEN BatchNorm (a module in eval mode inside a network that trains): mean = running_mean and
+ * invstd = 1 / sqrt(running_var + eps) are constants, so  dy = (gamma * invstd) * dz,  dbeta = sum dz,  dgamma = sum dz * xhat,
+ * xhat = (y - mean) * invstd.  Each form is ONE full-size pass: it writes dy and leaves partial[dn_reduce_blocks(rows, C)][C][2]
+ * = per-block sums of (dz, dz * xhat) (rows = the pooled pixels for the pool form; [..][C][4] for the tail: main branch at 0,
+ * downsample branch at 2), which dn_bn_frozen_finalize turns into dgamma, dbeta and the gradient of a conv bias in front of the
+ * BatchNorm.  C % 4 == 0.  Every form evaluates an element with the same device function: same bits whichever form handles it. */
+/* dn_bn_eval_affine that also hands out invstd[C] */
+int dn_bn_frozen_affine(int32_t C, const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                        float* scale, float* shift, float* invstd, dn_stream_t stream);
+/* gradient given as dz (a ReLU-less BatchNorm); overwritten with dy */
+int dn_bn_frozen_bwd(float* dz_dy, const float* y, const float* mean, const float* invstd, const float* gamma, int64_t rows, int32_t C,
+                     float* partial, dn_stream_t stream);
+/* gradient given as da under the pending ReLU: dz = da * [y * scale + shift > 0]; overwritten with dy */
+int dn_bn_frozen_bwd_relu(float* da_dy, const float* y, const float* scale, const float* shift, const float* mean, const float* invstd,
+                          const float* gamma, int64_t rows, int32_t C, float* partial, dn_stream_t stream);
+/* through the fused 2x2 max-pool: (dpooled, idx of dn_bn_relu_pool_fwd) expanded straight into dy [N,H,W,C]; dz is never written */
+int dn_bn_frozen_bwd_pool(const float* dpooled, const uint8_t* idx, const float* y, const float* mean, const float* invstd, const float* gamma,
+                          int32_t N, int32_t H, int32_t W, int32_t C, float* dy, float* partial, dn_stream_t stream);
+/* the tail of dn_bn_add_relu_fwd with frozen BatchNorms: m = gout * [out > 0]; dy = (gamma * invstd) * m; with r_mean / r_invstd /
+ * r_gamma (a frozen downsample BatchNorm) dr = (r_gamma * r_invstd) * m (overwrite), without them dr (+)= m (dr may be NULL). */
+int dn_bn_frozen_add_relu_bwd(const float* gout, const float* out, const float* y, const float* mean, const float* invstd, const float* gamma,
+                              const float* r, const float* r_mean, const float* r_invstd, const float* r_gamma, int64_t rows, int32_t C,
+                              float* dy, float* dr, int32_t dr_accumulate, float* partial, dn_stream_t stream);
+/* dbeta[c] = sum_r partial[r][c][offset], dgamma[c] = sum_r partial[r][c][offset + 1] (rows met in fp64, fixed order) and, unless
+ * dbias is NULL, dbias[c] = (gamma[c] * invstd[c]) * dbeta[c] = sum dy: the gradient of a conv bias in front of the BatchNorm. */
+int dn_bn_frozen_finalize(const float* partial, int32_t partial_rows, int32_t partial_stride, int32_t partial_offset, int32_t C,
+                          const float* gamma, const float* invstd, float* dgamma, float* dbeta, float* dbias, dn_stream_t stream);
+
 /* g_pre = g * act'(.) in place, using the stored POST-activation tensor y_post; also per-channel partial sums
  * [blocks][C] of g_pre (the conv bias gradient).  act: RELU / LEAKY(p0) / SIGMOID_AFFINE(p0,p1) / NONE. */
 int dn_act_bwd_reduce_from(const float* g_in, float* g_out, const float* y_post, int32_t act, float p0, float p1, int64_t rows, int32_t C,

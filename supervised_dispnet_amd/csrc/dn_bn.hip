@@ -1,6 +1,7 @@
 // BatchNorm on NHWC tensors, gfx950 only: batch statistics (the finalize of the conv epilogues' partial rows in both orders, the partial
 // rows of a materialised tensor, the eval-mode affine), BN + ReLU + MaxPool 2x2 forward, the backward (the column sums of dz -- after a
-// ReLU, through a pool --, their finalize in both orders, the apply pass in its dz / ReLU / pool forms) and the ResNet bottleneck tail.
+// ReLU, through a pool --, their finalize in both orders, the apply pass in its dz / ReLU / pool forms), the ResNet bottleneck tail, and
+// the backward of a FROZEN BatchNorm (running statistics: one pass per form that writes dy and takes the sums, plus its finalize).
 // HBM-bound; the column reductions are the two-stage ones of dn_colreduce.h.
 #include "dn_colreduce.h"
 #include "dn_fold.h"
@@ -90,14 +91,16 @@ __global__ void __launch_bounds__(256) colsum2_sliced_kernel(const float* __rest
   colsum2_sliced<false>(partial, rows, C, stride, offset, c0, C - c0 < 64 ? C - c0 : 64, out0, out1, red, threadIdx.x);
 }
 
+// invstd_out (nullable): what a frozen BatchNorm's backward needs besides the affine (dn_bn_frozen_affine)
 __global__ void bn_eval_affine_kernel(int C, const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
-                                      float* scale, float* shift) {
+                                      float* scale, float* shift, float* invstd_out) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C) {
     float invstd = 1.f / sqrtf(rv[c] + eps);
     float sc = gamma[c] * invstd;
     scale[c] = sc;
     shift[c] = beta[c] - rm[c] * sc;
+    if (invstd_out != nullptr) invstd_out[c] = invstd;
   }
 }
 
@@ -508,6 +511,219 @@ struct AddReluBwdOp {
   }
 };
 
+// ------------------------------------------------------------------------------ backward of a FROZEN BatchNorm (running statistics)
+// mean = running_mean, invstd = 1 / sqrt(running_var + eps) are constants of the step, so
+//   dy = (gamma * invstd) * dz,   dbeta = sum dz,   dgamma = sum dz * xhat,   xhat = (y - mean) * invstd
+// has no batch-mean terms: every form below is ONE full-size pass that writes dy and leaves the per-block partial rows of both sums
+// (dn_colreduce.h); bn_frozen_finalize_kernel meets the rows.  All forms go through this one function (contraction off): the same
+// element gets the same bits whichever form handles it (tests/test_gpu_bn_frozen.py).  Two rounded operations for dy (gamma * invstd,
+// the product), three for the dgamma term (a difference, two products).
+__device__ __forceinline__ float bn_frozen_bwd_value(float z, float yv, float mu, float is, float ga, float& term) {
+#pragma clang fp contract(off)
+  const float xhat = (yv - mu) * is;
+  term = z * xhat;
+  return (ga * is) * z;
+}
+
+// the pre-BatchNorm map is dead after this pass (its consumers' weight gradients ran before it): read it past the caches
+template <int V>
+__device__ __forceinline__ Vec<V> ldv_stream(const float* p) {
+  Vec<V> r;
+  if constexpr (V == 4) {
+    const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.v[i] = t[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) r.v[i] = p[i];
+  }
+  return r;
+}
+
+// RELU: g holds da, the gradient w.r.t. relu(bn(y)), dz = da * [y * scale + shift > 0]; else g holds dz.  g is overwritten with dy.
+template <bool RELU>
+struct BnFrozenBwdOp {
+  static constexpr int NACC = 2;
+  float* g_dy;
+  const float* y;
+  const float* scale;
+  const float* shift;
+  const float* mean;
+  const float* invstd;
+  const float* gamma;
+  int C;
+  template <int V>
+  __device__ __forceinline__ void apply(long long row, int c0, float (&acc)[V][2]) const {
+    const long long o = row * C + c0;
+    Vec<V> g = ldv<V>(g_dy + o);
+    const Vec<V> yv = ldv_stream<V>(y + o), mu = ldv<V>(mean + c0), is = ldv<V>(invstd + c0), ga = ldv<V>(gamma + c0);
+    Vec<V> sc, sh;
+    if constexpr (RELU) sc = ldv<V>(scale + c0), sh = ldv<V>(shift + c0);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      float z = g.v[e];
+      if constexpr (RELU) z = (yv.v[e] * sc.v[e] + sh.v[e] > 0.f) ? z : 0.f;
+      float term;
+      g.v[e] = bn_frozen_bwd_value(z, yv.v[e], mu.v[e], is.v[e], ga.v[e], term);
+      acc[e][0] += z;
+      acc[e][1] += term;
+    }
+    stv<V>(g_dy + o, g);
+  }
+};
+
+// Through the fused 2x2 max-pool: one POOLED pixel per visit, its (dpooled, idx) expanded straight into the four window pixels of dy;
+// the sparse dz is never written (train mode: PoolBwdOp for the sums, then bn_bwd_apply_pool_kernel).
+struct BnFrozenPoolBwdOp {
+  static constexpr int NACC = 2;
+  const float* dpooled;
+  const uint8_t* idx;
+  const float* y;
+  const float* mean;
+  const float* invstd;
+  const float* gamma;
+  float* dy;
+  int PH, PW, H, W, C;
+  template <int V>
+  __device__ __forceinline__ void apply(long long row, int c0, float (&acc)[V][2]) const {
+    const int px = (int)(row % PW);
+    const long long t = row / PW;
+    const int py = (int)(t % PH), n = (int)(t / PH);
+    const Vec<V> dp = ldv<V>(dpooled + row * C + c0);
+    const Vec<V> mu = ldv<V>(mean + c0), is = ldv<V>(invstd + c0), ga = ldv<V>(gamma + c0);
+    const long long base = (((long long)n * H + 2 * py) * W + 2 * px) * C + c0;
+    unsigned codes = 0;
+    if constexpr (V == 4) codes = *reinterpret_cast<const unsigned*>(idx + row * C + c0);
+    Vec<V> yq[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) yq[q] = ldv_stream<V>(y + base + ((long long)(q >> 1) * W + (q & 1)) * C);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int code = V == 4 ? (int)((codes >> (8 * e)) & 0xffu) : (int)idx[row * C + c0 + e];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float z = ((code & 4) && (code & 3) == q) ? dp.v[e] : 0.f;
+        float term;
+        yq[q].v[e] = bn_frozen_bwd_value(z, yq[q].v[e], mu.v[e], is.v[e], ga.v[e], term);
+        acc[e][0] += z;
+        acc[e][1] += term;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) stv<V>(dy + base + ((long long)(q >> 1) * W + (q & 1)) * C, yq[q]);
+  }
+};
+
+// The residual tail out = relu(bn(y) + r') with both BatchNorms frozen: from d(out) the masked gradient m = d(out) * [out > 0] becomes
+// dy of the main branch and, in the same pass, dr of a frozen downsample branch (r_mean given) or the plain m of an identity branch
+// (overwritten or accumulated); sums of both branches (partial[blk][C][4]: main at 0, downsample at 2).
+struct BnFrozenAddReluBwdOp {
+  static constexpr int NACC = 4;
+  const float* gout;
+  const float* out;
+  const float* y;
+  const float* mean;
+  const float* invstd;
+  const float* gamma;
+  const float* r;
+  const float* r_mean;     // nullable: plain identity
+  const float* r_invstd;
+  const float* r_gamma;
+  float* dy;
+  float* dr;
+  int dr_accumulate;
+  int C;
+  template <int V>
+  __device__ __forceinline__ void apply(long long row, int c0, float (&acc)[V][4]) const {
+    const long long o = row * C + c0;
+    const Vec<V> g = ldv<V>(gout + o), ov = ldv<V>(out + o), yv = ldv_stream<V>(y + o);
+    const Vec<V> mu = ldv<V>(mean + c0), is = ldv<V>(invstd + c0), ga = ldv<V>(gamma + c0);
+    Vec<V> m, d;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      m.v[e] = ov.v[e] > 0.f ? g.v[e] : 0.f;
+      float term;
+      d.v[e] = bn_frozen_bwd_value(m.v[e], yv.v[e], mu.v[e], is.v[e], ga.v[e], term);
+      acc[e][0] += m.v[e];
+      acc[e][1] += term;
+    }
+    stv<V>(dy + o, d);
+    if (r_mean != nullptr) {
+      const Vec<V> rv = ldv_stream<V>(r + o), rm = ldv<V>(r_mean + c0), ri = ldv<V>(r_invstd + c0), rg = ldv<V>(r_gamma + c0);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        float term;
+        d.v[e] = bn_frozen_bwd_value(m.v[e], rv.v[e], rm.v[e], ri.v[e], rg.v[e], term);
+        acc[e][2] += m.v[e];
+        acc[e][3] += term;
+      }
+      stv<V>(dr + o, d);
+    } else if (dr != nullptr) {
+      if (dr_accumulate) {
+        Vec<V> a = ldv<V>(dr + o);
+#pragma unroll
+        for (int e = 0; e < V; ++e) a.v[e] += m.v[e];
+        stv<V>(dr + o, a);
+      } else {
+        stv<V>(dr + o, m);
+      }
+    }
+  }
+};
+
+// The partial rows of a frozen pass become dbeta[c] = sum_r partial[r][c][offset], dgamma[c] = sum_r partial[r][c][offset + 1] and,
+// when asked for, the gradient of a conv bias in front of the BatchNorm: with frozen statistics it is no longer identically zero,
+//   dbias[c] = sum dy = (gamma[c] * invstd[c]) * dbeta[c]      (two fp32 products on the ROUNDED dbeta, contraction off),
+// at no extra pass.  The rows meet in double precision in a fixed order: the sliced order of dn_fold.h for up to kFoldMaxRows rows
+// (one block per 64 channels), else colsum2_finalize_kernel's (one block per channel).
+__device__ __forceinline__ float bn_frozen_dbias(float ga, float is, float db) {
+#pragma clang fp contract(off)
+  return (ga * is) * db;
+}
+
+__global__ void __launch_bounds__(256) bn_frozen_finalize_sliced_kernel(const float* __restrict__ partial, int rows, int C, int stride, int offset,
+                                                                        const float* __restrict__ gamma, const float* __restrict__ invstd,
+                                                                        float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                        float* __restrict__ dbias) {
+  __shared__ double red[2 * kFoldSlices * 64];
+  const int c0 = blockIdx.x * 64;
+  const int nlive = C - c0 < 64 ? C - c0 : 64;
+  colsum2_sliced<false>(partial, rows, C, stride, offset, c0, nlive, dbeta, dgamma, red, threadIdx.x);
+  // (thread (channel, slice 0) wrote dbeta[c] itself: program order, no barrier)
+  const int cl = threadIdx.x & 63;
+  if (dbias != nullptr && (threadIdx.x >> 6) == 0 && cl < nlive) dbias[c0 + cl] = bn_frozen_dbias(gamma[c0 + cl], invstd[c0 + cl], dbeta[c0 + cl]);
+}
+
+__global__ void __launch_bounds__(256) bn_frozen_finalize_kernel(const float* __restrict__ partial, int rows, int C, int stride, int offset,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ invstd,
+                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dbias) {
+  const int c = blockIdx.x;
+  double s0 = 0.0, s1 = 0.0;
+#pragma unroll 4
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    const float* q = partial + ((long long)r * C + c) * stride + offset;
+    s0 += (double)q[0];
+    s1 += (double)q[1];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s0 += __shfl_xor(s0, o);
+    s1 += __shfl_xor(s1, o);
+  }
+  __shared__ double red[2][4];
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = s0;
+    red[1][threadIdx.x >> 6] = s1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float db = (float)((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]));
+    dbeta[c] = db;
+    dgamma[c] = (float)((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
+    if (dbias != nullptr) dbias[c] = bn_frozen_dbias(gamma[c], invstd[c], db);
+  }
+}
+
 // The apply pass of both entry points below.  Hoisted form: a grid whose stride (blocks x 256 threads) is a multiple of the channel
 // groups G = C / 4 -- per = lcm(G, 256) / 256 = G / gcd(G, 256) blocks span a whole number of pixels, and the grid is rounded up to a
 // multiple of per --, unless that takes more than 64 blocks: then the plain loop.
@@ -564,8 +780,72 @@ int dn_bn_eval_affine(int32_t C, const float* gamma, const float* beta, const fl
                       float* scale, float* shift, dn_stream_t stream) {
   DN_REQUIRE(C > 0 && gamma && beta && running_mean && running_var && scale && shift, DN_ERR_BAD_ARG, "dn_bn_eval_affine: bad argument");
   DN_LAUNCH(bn_eval_affine_kernel, dim3((C + 255) / 256), dim3(256), 0, as_stream(stream), C, gamma, beta, running_mean,
-                     running_var, eps, scale, shift);
+                     running_var, eps, scale, shift, (float*)nullptr);
   return check_launch("bn_eval_affine_kernel");
+}
+
+int dn_bn_frozen_affine(int32_t C, const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                        float* scale, float* shift, float* invstd, dn_stream_t stream) {
+  DN_REQUIRE(C > 0 && gamma && beta && running_mean && running_var && scale && shift && invstd, DN_ERR_BAD_ARG,
+             "dn_bn_frozen_affine: bad argument");
+  DN_LAUNCH(bn_eval_affine_kernel, dim3((C + 255) / 256), dim3(256), 0, as_stream(stream), C, gamma, beta, running_mean,
+                     running_var, eps, scale, shift, invstd);
+  return check_launch("bn_eval_affine_kernel");
+}
+
+int dn_bn_frozen_bwd(float* dz_dy, const float* y, const float* mean, const float* invstd, const float* gamma, int64_t rows, int32_t C,
+                     float* partial, dn_stream_t stream) {
+  DN_REQUIRE(dz_dy && y && mean && invstd && gamma && partial && rows > 0 && C > 0, DN_ERR_BAD_ARG, "dn_bn_frozen_bwd: bad argument");
+  DN_REQUIRE(C % 4 == 0, DN_ERR_UNSUPPORTED, "dn_bn_frozen_bwd: need C%%4==0");
+  BnFrozenBwdOp<false> op{dz_dy, y, nullptr, nullptr, mean, invstd, gamma, C};
+  return launch_colreduce(op, rows, C, partial, as_stream(stream), "bn_frozen_bwd");
+}
+
+int dn_bn_frozen_bwd_relu(float* da_dy, const float* y, const float* scale, const float* shift, const float* mean, const float* invstd,
+                          const float* gamma, int64_t rows, int32_t C, float* partial, dn_stream_t stream) {
+  DN_REQUIRE(da_dy && y && scale && shift && mean && invstd && gamma && partial && rows > 0 && C > 0, DN_ERR_BAD_ARG,
+             "dn_bn_frozen_bwd_relu: bad argument");
+  DN_REQUIRE(C % 4 == 0, DN_ERR_UNSUPPORTED, "dn_bn_frozen_bwd_relu: need C%%4==0");
+  BnFrozenBwdOp<true> op{da_dy, y, scale, shift, mean, invstd, gamma, C};
+  return launch_colreduce(op, rows, C, partial, as_stream(stream), "bn_frozen_bwd_relu");
+}
+
+int dn_bn_frozen_bwd_pool(const float* dpooled, const uint8_t* idx, const float* y, const float* mean, const float* invstd, const float* gamma,
+                          int32_t N, int32_t H, int32_t W, int32_t C, float* dy, float* partial, dn_stream_t stream) {
+  DN_REQUIRE(dpooled && idx && y && mean && invstd && gamma && dy && partial && N > 0 && H > 0 && W > 0 && C > 0, DN_ERR_BAD_ARG,
+             "dn_bn_frozen_bwd_pool: bad argument");
+  DN_REQUIRE(C % 4 == 0 && H % 2 == 0 && W % 2 == 0, DN_ERR_UNSUPPORTED, "dn_bn_frozen_bwd_pool: need C%%4==0 and even H,W");
+  BnFrozenPoolBwdOp op{dpooled, idx, y, mean, invstd, gamma, dy, H / 2, W / 2, H, W, C};
+  return launch_colreduce(op, (long long)N * (H / 2) * (W / 2), C, partial, as_stream(stream), "bn_frozen_bwd_pool");
+}
+
+int dn_bn_frozen_add_relu_bwd(const float* gout, const float* out, const float* y, const float* mean, const float* invstd, const float* gamma,
+                              const float* r, const float* r_mean, const float* r_invstd, const float* r_gamma, int64_t rows, int32_t C,
+                              float* dy, float* dr, int32_t dr_accumulate, float* partial, dn_stream_t stream) {
+  DN_REQUIRE(gout && out && y && mean && invstd && gamma && dy && partial && rows > 0 && C > 0, DN_ERR_BAD_ARG,
+             "dn_bn_frozen_add_relu_bwd: bad argument");
+  DN_REQUIRE(C % 4 == 0, DN_ERR_UNSUPPORTED, "dn_bn_frozen_add_relu_bwd: need C%%4==0");
+  DN_REQUIRE((r_mean == nullptr) == (r_invstd == nullptr) && (r_mean == nullptr) == (r_gamma == nullptr), DN_ERR_BAD_ARG,
+             "dn_bn_frozen_add_relu_bwd: r_mean / r_invstd / r_gamma go together");
+  DN_REQUIRE(r_mean == nullptr || (r && dr), DN_ERR_BAD_ARG, "dn_bn_frozen_add_relu_bwd: the downsample branch needs r and dr");
+  BnFrozenAddReluBwdOp op{gout, out, y, mean, invstd, gamma, r, r_mean, r_invstd, r_gamma, dy, dr, dr_accumulate, C};
+  return launch_colreduce(op, rows, C, partial, as_stream(stream), "bn_frozen_add_relu_bwd");
+}
+
+int dn_bn_frozen_finalize(const float* partial, int32_t partial_rows, int32_t partial_stride, int32_t partial_offset, int32_t C,
+                          const float* gamma, const float* invstd, float* dgamma, float* dbeta, float* dbias, dn_stream_t stream) {
+  DN_REQUIRE(partial && dgamma && dbeta && partial_rows > 0 && C > 0, DN_ERR_BAD_ARG, "dn_bn_frozen_finalize: bad argument");
+  DN_REQUIRE(dbias == nullptr || (gamma && invstd), DN_ERR_BAD_ARG, "dn_bn_frozen_finalize: the bias gradient needs gamma and invstd");
+  DN_REQUIRE(partial_stride >= 2 && partial_offset >= 0 && partial_offset + 1 < partial_stride, DN_ERR_BAD_ARG,
+             "dn_bn_frozen_finalize: partial layout");
+  hipStream_t s = as_stream(stream);
+  if (partial_rows <= kFoldMaxRows && (partial_stride & 1) == 0 && (partial_offset & 1) == 0 && (reinterpret_cast<uintptr_t>(partial) & 7) == 0)
+    DN_LAUNCH(bn_frozen_finalize_sliced_kernel, dim3((C + 63) / 64), dim3(256), 0, s, partial, partial_rows, C, partial_stride, partial_offset, gamma,
+              invstd, dgamma, dbeta, dbias);
+  else
+    DN_LAUNCH(bn_frozen_finalize_kernel, dim3(C), dim3(256), 0, s, partial, partial_rows, C, partial_stride, partial_offset, gamma, invstd, dgamma,
+              dbeta, dbias);
+  return check_launch("bn_frozen_finalize");
 }
 
 int32_t dn_bn_stats_rows(int64_t rows) { return (int32_t)((rows + kBnTileRows - 1) / kBnTileRows); }

@@ -417,7 +417,7 @@ class BnSums:
 class Act:
     """An NHWC fp32 activation [N,H,W,C] plus what the engine needs to know about it."""
     __slots__ = ("t", "N", "H", "W", "C", "scale", "shift", "mean", "invstd", "grad", "grad_is_dz", "bn_sums", "needs_grad", "strides",
-                 "no_relu", "planar", "pool_src", "recip_t", "bn_owner", "seed_borrow", "grad_borrowed")
+                 "no_relu", "planar", "pool_src", "recip_t", "bn_owner", "seed_borrow", "grad_borrowed", "frozen", "fz_sums")
 
     def __init__(self, t, N, H, W, C, strides=None, needs_grad=True):
         self.t = t
@@ -440,6 +440,10 @@ class Act:
         self.seed_borrow = False        # the producing block reads a seeded gradient WITHOUT writing it (block_conv_act: out-of-place
                                         # activation backward): seed_grad() may hand the framework's tensor over instead of a copy
         self.grad_borrowed = False      # .grad is the framework's tensor: read-only
+        self.frozen = None              # (running_mean, invstd, gamma) of a FROZEN BatchNorm pending on this activation (its module is in eval mode
+                                        # while a backward is recorded); .mean / .invstd stay None: no batch statistics exist
+        self.fz_sums = None             # BnSums a frozen residual tail left when it wrote dL/dy into .grad itself (block_bn_add_relu): the
+                                        # frozen BatchNorm backward then only finishes d(gamma), d(beta), d(conv bias)
         self.needs_grad = needs_grad
         self.strides = strides or (H * W * C, W * C, C, 1)   # (n, h, w, c) element strides
 
@@ -899,7 +903,9 @@ def conv_dgrad(layer, dy, N, OH, OW, pieces, in_hw):
     d.act = ACT_NONE
     # BatchNorm backward of the layer below: when this call is the (first) writer of the gradient of a pre-BatchNorm activation with a
     # pending BN + ReLU, let its epilogue take the column sums (sum dz, sum dz * xhat) the BatchNorm backward needs -- one full read of
-    # the gradient and one launch less per layer (dn_conv_desc.bnb_*); bn_backward() skips its sums pass when it finds .bn_sums
+    # the gradient and one launch less per layer (dn_conv_desc.bnb_*); bn_backward() skips its sums pass when it finds .bn_sums.
+    # A FROZEN BatchNorm below (a.mean is None, a.frozen set) stays excluded on purpose: its backward is one pass that has to read the
+    # gradient and y anyway to write dy = k * dz, and takes the sums in that pass -- sums from this epilogue would save it nothing
     _splitk_workspace(d, dy.device)
     fuse = None
     if BN_SUMS_FUSION and len(targets) == 1 and not layer.transposed and not layer.reflect:
@@ -1038,13 +1044,89 @@ class GradSink:
         return self.grads.get(id(param))
 
 
-def bn_backward(y, bn, sink, training):
+def _bn_frozen_affine(y, bn, record):
+    """Running statistics of `bn` folded into the (scale, shift) pending on `y`; no buffer of bn moves.  `record`: a backward may
+    follow -- invstd is kept too and y.frozen marks the BatchNorm as frozen for the block helpers' backward."""
+    Cn, dev = y.C, y.t.device
+    y.scale = torch.empty(Cn, dtype=torch.float32, device=dev)
+    y.shift = torch.empty(Cn, dtype=torch.float32, device=dev)
+    if record:
+        invstd = torch.empty(Cn, dtype=torch.float32, device=dev)
+        _lib.call("dn_bn_frozen_affine", Cn, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                  bn.running_var.data_ptr(), bn.eps, y.scale.data_ptr(), y.shift.data_ptr(), invstd.data_ptr(), _stream())
+        y.frozen = (bn.running_mean, invstd, bn.weight)
+    else:
+        _lib.call("dn_bn_eval_affine", Cn, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                  bn.running_var.data_ptr(), bn.eps, y.scale.data_ptr(), y.shift.data_ptr(), _stream())
+
+
+def _bn_backward_frozen(y, bn, sink, conv_bias, defer):
+    """bn_backward for a frozen BatchNorm: dy = (gamma * invstd) * dz has no batch-mean terms, so ONE pass over the gradient writes dL/dy
+    and leaves the partial rows of sum dz, sum dz * xhat (dn_bn_frozen_bwd / _relu / _pool; a frozen residual tail has done both already:
+    y.fz_sums).  The finalize -- d(gamma), d(beta) and d(conv_bias) = gamma * invstd * d(beta), no longer zero -- is only read by the
+    optimizer: with `defer` (a list) it is appended as (finish, partial) for conv_wgrad(first=...) to run on the weight-gradient stream."""
+    g, Cn, dev = y.grad, y.C, y.t.device
+    mean, invstd = y.frozen[:2]
+    sums, y.fz_sums = y.fz_sums, None
+    if sums is None:
+        gamma = bn.weight.data_ptr()
+        if y.pool_src is not None:            # gradient through the 2x2 max-pool: (dpooled, idx) expanded into dy here
+            dpooled, pidx = y.pool_src
+            nblk = _lib.load().dn_reduce_blocks(y.rows // 4, Cn)
+            sums = BnSums(torch.empty((nblk, Cn, 2), dtype=torch.float32, device=dev), nblk)
+            hbm_call("dn::colreduce_kernel<dn::BnFrozenPoolBwdOp, 4>", y.rows * Cn * 8 + y.rows * Cn * 5 // 4, "dn_bn_frozen_bwd_pool",
+                     dpooled.data_ptr(), pidx.data_ptr(), y.t.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma, y.N, y.H, y.W, Cn,
+                     g.data_ptr(), sums.partial.data_ptr(), _stream())
+            y.pool_src = None
+        else:
+            nblk = _lib.load().dn_reduce_blocks(y.rows, Cn)
+            sums = BnSums(torch.empty((nblk, Cn, 2), dtype=torch.float32, device=dev), nblk)
+            if y.grad_is_dz:
+                hbm_call("dn::colreduce_kernel<dn::BnFrozenBwdOp<false>, 4>", y.rows * Cn * 12, "dn_bn_frozen_bwd", g.data_ptr(), y.t.data_ptr(),
+                         mean.data_ptr(), invstd.data_ptr(), gamma, y.rows, Cn, sums.partial.data_ptr(), _stream())
+            else:
+                if y.no_relu:
+                    raise RuntimeError("a ReLU-less BatchNorm output must be consumed by block_bn_add_relu / block_bn_plain")
+                hbm_call("dn::colreduce_kernel<dn::BnFrozenBwdOp<true>, 4>", y.rows * Cn * 12, "dn_bn_frozen_bwd_relu", g.data_ptr(),
+                         y.t.data_ptr(), y.scale.data_ptr(), y.shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma, y.rows, Cn,
+                         sums.partial.data_ptr(), _stream())
+    y.bn_sums = None                          # g is dL/dy now
+    dgamma, dbeta = sink.dest_or_new(bn.weight), sink.dest_or_new(bn.bias)
+    dbias = sink.dest_or_new(conv_bias) if conv_bias is not None else None
+    home = _stream()
+
+    def finish():
+        h = _stream()
+        _lib.call("dn_bn_frozen_finalize", sums.partial.data_ptr(), sums.rows, sums.stride, sums.offset, Cn, bn.weight.data_ptr(),
+                  invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dbias), h)
+        if h != home:                         # on the weight-gradient side stream: what it touches was allocated on the main one
+            cur = torch.cuda.current_stream()
+            cross_stream_use(invstd, cur)
+            for prm, t in ((bn.weight, dgamma), (bn.bias, dbeta), (conv_bias, dbias)):
+                if t is not None and sink.dest(prm) is None:
+                    cross_stream_use(t, cur)
+        sink.put(bn.weight, dgamma)
+        sink.put(bn.bias, dbeta)
+        if dbias is not None:
+            sink.put(conv_bias, dbias)
+
+    if defer is not None:
+        defer.append((finish, sums.partial))
+    else:
+        finish()
+    return g
+
+
+def bn_backward(y, bn, sink, conv_bias=None, defer=None):
     """BatchNorm backward of an activation stored pre-BN with the affine pending (block_conv_bn, block_upproject): y.grad holds
     dL/d(relu(bn(y))) -- or dz with its column sums in y.bn_sums when y.grad_is_dz -- and becomes dL/dy in place; d(gamma), d(beta) go
-    to the sink.  Returns the gradient tensor."""
+    to the sink.  Returns the gradient tensor.  Batch or running statistics: decided by what the forward left on `y` (y.frozen: the
+    module was in eval mode).  `conv_bias`, `defer`: the frozen form only (_bn_backward_frozen)."""
     g, y_t, Cn, dev = y.grad, y.t, y.C, y.t.device
-    if not training:
-        raise NotImplementedError("backward through eval-mode BatchNorm (frozen statistics) is not implemented")
+    if y.frozen is not None:
+        return _bn_backward_frozen(y, bn, sink, conv_bias, defer)
+    if y.mean is None:
+        raise RuntimeError("bn_backward: the forward of this BatchNorm was not recorded (neither batch statistics nor a frozen state on it)")
     relu_pending = not y.grad_is_dz           # g is dL/d(relu output): the mask is applied by the kernels below
     sums = y.bn_sums
     if relu_pending and (sums is None or BN_MATERIALIZE_DZ):      # (sums from the epilogue of the kernel that wrote g, conv_dgrad, are
@@ -1096,54 +1178,69 @@ def _bn_finalize(bn, partial, prow, count, conv_bias, mean, invstd, scale, shift
               scale.data_ptr(), shift.data_ptr(), nbt, _stream())
 
 
-def _bn_pending(y, bn, partial, prow, training, conv_bias=None):
+def _bn_pending(y, bn, partial, prow, training, conv_bias=None, record=False):
     """Fold batch statistics (training: from `partial`, also updating the running buffers) or running statistics (eval) of `bn` into the
-    per-channel (scale, shift) pending on `y`."""
+    per-channel (scale, shift) pending on `y`.  `record`: a backward may follow (the eval form then keeps what it needs: y.frozen)."""
     Cn, dev = y.C, y.t.device
+    if not training:
+        _bn_frozen_affine(y, bn, record)
+        return
     y.scale = torch.empty(Cn, dtype=torch.float32, device=dev)
     y.shift = torch.empty(Cn, dtype=torch.float32, device=dev)
-    if training:
-        y.mean = torch.empty(Cn, dtype=torch.float32, device=dev)
-        y.invstd = torch.empty(Cn, dtype=torch.float32, device=dev)
-        _bn_finalize(bn, partial, prow, y.rows, conv_bias, y.mean, y.invstd, y.scale, y.shift, _nbt_ptr(bn))
-    else:
-        _lib.call("dn_bn_eval_affine", Cn, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                  bn.running_var.data_ptr(), bn.eps, y.scale.data_ptr(), y.shift.data_ptr(), _stream())
+    y.mean = torch.empty(Cn, dtype=torch.float32, device=dev)
+    y.invstd = torch.empty(Cn, dtype=torch.float32, device=dev)
+    _bn_finalize(bn, partial, prow, y.rows, conv_bias, y.mean, y.invstd, y.scale, y.shift, _nbt_ptr(bn))
 
 
 # ------------------------------------------------------------------------------------------------- block helpers
 def block_conv_bn(tape, sink, x_piece, layer, bn, training, relu=True):
     """conv3x3 -> BatchNorm (batch statistics when training) -> ReLU, with the BN-apply+ReLU left pending on the result
     (the consumer's loader applies it).  Reference: torchvision vgg16_bn features triplets used at
-    models/Disp_vgg_BN.py:137-141."""
+    models/Disp_vgg_BN.py:137-141.
+    Batch or running statistics is decided per module, from `bn.training` (net.train() followed by bn.eval() freezes this BatchNorm as
+    in PyTorch); `training`, the NETWORK's flag the models pass, is not consulted for it.  A frozen BatchNorm takes no statistics in the
+    conv epilogue, moves no buffer, and the stored pre-BatchNorm map includes the conv bias (the epilogue adds it) -- the quantity the
+    running mean was accumulated on (dn_bn_finalize shifts the batch mean by the bias), so xhat = (y - running_mean) * invstd."""
     xa = x_piece.act
     dev = xa.t.device
     Cn = layer.Cout
+    if not bn.training:
+        y_t, _, _ = conv_forward(layer, [x_piece], ACT_NONE)
+        OH, OW = y_t.shape[1], y_t.shape[2]
+        y = Act(y_t, xa.N, OH, OW, Cn)
+        y.no_relu = not relu
+        _bn_frozen_affine(y, bn, tape.recording)
+
+        def backward_frozen():
+            if y.grad is None:
+                return
+            fin = []
+            g = bn_backward(y, bn, sink, conv_bias=layer.m.bias, defer=fin)
+            conv_wgrad(layer, [x_piece], g, (OH, OW), out=sink.dest(layer.m.weight), sink=sink, first=fin[0])
+            conv_dgrad(layer, g, xa.N, OH, OW, [x_piece], (xa.H, xa.W))
+            y.grad = None
+
+        tape.push(backward_frozen)
+        return y
     scale = torch.empty(Cn, dtype=torch.float32, device=dev)
     shift = torch.empty(Cn, dtype=torch.float32, device=dev)
-    mean = invstd = fold = nbt = None
-    if training:
-        mean = torch.empty(Cn, dtype=torch.float32, device=dev)
-        invstd = torch.empty(Cn, dtype=torch.float32, device=dev)
-        nbt = _nbt_ptr(bn)
-        fold = [bn, mean, invstd, scale, shift, nbt]
-    y_t, partial, prow = conv_forward(layer, [x_piece], ACT_NONE, bn_stats=training, bn_fold=fold)
+    mean = torch.empty(Cn, dtype=torch.float32, device=dev)
+    invstd = torch.empty(Cn, dtype=torch.float32, device=dev)
+    nbt = _nbt_ptr(bn)
+    fold = [bn, mean, invstd, scale, shift, nbt]
+    y_t, partial, prow = conv_forward(layer, [x_piece], ACT_NONE, bn_stats=True, bn_fold=fold)
     OH, OW = y_t.shape[1], y_t.shape[2]
     y = Act(y_t, xa.N, OH, OW, Cn)
     y.no_relu = not relu
     y.scale, y.shift, y.mean, y.invstd = scale, shift, mean, invstd
     y.bn_owner = (bn, sink)
-    if training:
-        if fold[0] is not True:              # (True: the convolution's last-arriving blocks finished the statistics themselves)
-            _bn_finalize(bn, partial, prow, y.rows, layer.m.bias, mean, invstd, scale, shift, nbt)
-    else:
-        _lib.call("dn_bn_eval_affine", Cn, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                  bn.running_var.data_ptr(), bn.eps, y.scale.data_ptr(), y.shift.data_ptr(), _stream())
+    if fold[0] is not True:              # (True: the convolution's last-arriving blocks finished the statistics themselves)
+        _bn_finalize(bn, partial, prow, y.rows, layer.m.bias, mean, invstd, scale, shift, nbt)
 
     def backward():
         if y.grad is None:
             return
-        g = bn_backward(y, bn, sink, training)
+        g = bn_backward(y, bn, sink)
         # g is now dL/d(conv output).  The conv bias sits in front of a BatchNorm: its gradient is identically zero in
         # exact arithmetic (BN removes the mean); the reference's value is rounding noise.  We store exact zeros.
         if layer.m.bias is not None:
@@ -1167,6 +1264,14 @@ def block_pool(tape, y):
 
     def backward():
         if p.grad is None:
+            return
+        if y.frozen is not None:
+            # frozen BatchNorm below: no pass here at all -- its one backward pass (dn_bn_frozen_bwd_pool) expands (dpooled, idx) into dy
+            # and takes the sums alongside
+            y.grad = y.new_like()
+            y.grad_is_dz = True
+            y.pool_src = (p.grad, idx)
+            p.grad = None
             return
         nblk = _lib.load().dn_reduce_blocks(p.rows, y.C)
         sums = y.bn_sums = BnSums(torch.empty((nblk, y.C, 2), dtype=torch.float32, device=dev), nblk)
@@ -1193,7 +1298,10 @@ def block_conv_act(tape, sink, pieces, layer, act, p0=0.0, p1=0.0, out_hw=None, 
     """conv / conv-transpose over virtually concatenated pieces + bias + activation in the epilogue.
     Reference: Conv2dBlock1 / ConvTranspose2dBlock1 / predict_disp (models/Disp_vgg_BN.py:40-70).
     `stat_bn`: a BatchNorm2d whose output the reference computes and DISCARDS (models/Disp_res_50.py:141-145: `bn1 =
-    self.bn1(conv1); relu1 = self.relu(conv1)`): only its running statistics are updated, from the conv epilogue's sums."""
+    self.bn1(conv1); relu1 = self.relu(conv1)`): only its running statistics are updated, from the conv epilogue's sums -- unless that
+    module is in eval mode (frozen): then nothing of it moves and no statistics are taken."""
+    if stat_bn is not None and not stat_bn.training:
+        stat_bn = None
     a0 = pieces[0].act
     in_hw = (a0.H * (2 if pieces[0].up else 1), a0.W * (2 if pieces[0].up else 1))
     # (a DISPARITY head: alpha * sigmoid + beta with beta > 0, in training or eval; PoseExpNet's explainability masks are sigmoid heads
@@ -1356,6 +1464,10 @@ def block_bn_add_relu(tape, y, r):
     ds = r is not None and r.no_relu
     if r is not None and not ds and r.scale is not None:
         raise RuntimeError("block_bn_add_relu: the identity branch must be a plain activation")
+    if ds and tape.recording and (y.frozen is None) != (r.frozen is None):
+        # one pass serves both branches, in one mode; a tail with one BatchNorm frozen and the other on batch statistics is refused
+        raise RuntimeError("block_bn_add_relu: the main-branch BatchNorm and the downsample BatchNorm of one residual block must both be "
+                           "frozen (eval mode) or both train; freeze or unfreeze them together")
     dev = y.t.device
     out_t = y.new_like()
     _lib.call("dn_bn_add_relu_fwd", y.t.data_ptr(), y.scale.data_ptr(), y.shift.data_ptr(), r.t.data_ptr() if r is not None else None,
@@ -1365,10 +1477,29 @@ def block_bn_add_relu(tape, y, r):
     def backward():
         if out.grad is None:
             return
-        if y.mean is None:
-            raise NotImplementedError("backward through eval-mode BatchNorm (frozen statistics) is not implemented")
         nblk = _lib.load().dn_reduce_blocks(y.rows, y.C)
         partial = torch.empty((nblk, y.C, 4), dtype=torch.float32, device=dev)
+        if y.frozen is not None:
+            # frozen BatchNorm(s): this ONE pass writes dL/dy of the main branch and dL/dr of a frozen downsample branch (or the masked
+            # gradient of an identity branch) and takes both branches' sums; the producers' bn_backward only finishes them (.fz_sums)
+            y.grad = y.new_like()
+            y.fz_sums = BnSums(partial, nblk, 4, 0)
+            dr, acc = None, False
+            if ds:
+                dr = r.grad = r.new_like()
+                r.fz_sums = BnSums(partial, nblk, 4, 2)
+            elif r is not None and r.needs_grad:
+                dr, acc = r.grad_dest()
+            bn_w, r_w = y.frozen[2], (r.frozen[2] if ds else None)
+            hbm_call("dn::colreduce_kernel<dn::BnFrozenAddReluBwdOp, 4>", y.rows * y.C * (24 if ds else 20 if dr is not None else 16),
+                     "dn_bn_frozen_add_relu_bwd", out.grad.data_ptr(), out_t.data_ptr(), y.t.data_ptr(), y.frozen[0].data_ptr(),
+                     y.frozen[1].data_ptr(), bn_w.data_ptr(), r.t.data_ptr() if r is not None else None,
+                     r.frozen[0].data_ptr() if ds else None, r.frozen[1].data_ptr() if ds else None, r_w.data_ptr() if ds else None,
+                     y.rows, y.C, y.grad.data_ptr(), _ptr(dr), int(acc), partial.data_ptr(), _stream())
+            out.grad = None
+            return
+        if y.mean is None:
+            raise RuntimeError("block_bn_add_relu: the forward of this BatchNorm was not recorded")
         y.grad = y.new_like()
         y.grad_is_dz = True
         y.bn_sums = BnSums(partial, nblk, 4, 0)
@@ -1487,8 +1618,11 @@ def block_bn_plain(tape, y):
     def backward():
         if out.grad is None:
             return
+        if y.frozen is not None:              # frozen: d(out) IS dz, and the producer's one pass (dn_bn_frozen_bwd) takes the sums itself
+            y.grad, y.grad_is_dz, out.grad = out.grad, True, None
+            return
         if y.mean is None:
-            raise NotImplementedError("backward through eval-mode BatchNorm (frozen statistics) is not implemented")
+            raise RuntimeError("block_bn_plain: the forward of this BatchNorm was not recorded")
         dev = y.t.device
         nblk = _lib.load().dn_reduce_blocks(y.rows, y.C)
         sums = BnSums(torch.empty((nblk, y.C, 2), dtype=torch.float32, device=dev), nblk)
@@ -1565,11 +1699,11 @@ def block_upproject(tape, sink, x, up, rt, training):
         o = Act(o_t, N, 2 * H, 2 * W, Cn)
         bn = up.bn1_1 if br == 1 else up.bn1_2
         partial, prow = None, 0
-        if training:
+        if bn.training:                       # (per module: a frozen BatchNorm takes no statistics)
             prow = _lib.load().dn_bn_stats_rows(o.rows)
             partial = torch.empty((prow, Cn, 2), dtype=torch.float32, device=dev)
             _lib.call("dn_bn_stats_partial", o_t.data_ptr(), o.rows, Cn, partial.data_ptr(), _stream())
-        _bn_pending(o, bn, partial, prow, training)
+        _bn_pending(o, bn, partial, prow, bn.training, record=tape.recording)
         maps.append(o)
     o1, o2 = maps
     o2.no_relu = True
@@ -1581,7 +1715,7 @@ def block_upproject(tape, sink, x, up, rt, training):
                 continue
             layer = rt["t%d" % br]
             bn = up.bn1_1 if br == 1 else up.bn1_2
-            g = bn_backward(o, bn, sink, training)                      # dL/d(interleaved pre-BatchNorm map)
+            g = bn_backward(o, bn, sink)                                # dL/d(interleaved pre-BatchNorm map)
             lib = _lib.load()
             ws = torch.empty(lib.dn_phase_colsum_workspace_bytes(Cn) // 4, dtype=torch.float32, device=dev)
             db4 = torch.empty((4, Cn), dtype=torch.float32, device=dev)

@@ -102,6 +102,10 @@ def build_parser():
                         "setting is eligible (at the reference's own -b4 the eager step is host-bound: 5.0 ms against 3.5 taped); an "
                         "ineligible setting runs eagerly without a word unless --tape was given explicitly")
     p.add_argument("--no-tape", dest="tape", action="store_false", help="always issue the training step as eager launches")
+    p.add_argument("--freeze-bn", action="store_true",
+                   help="fine-tune with frozen BatchNorm statistics: every BatchNorm of the depth network runs in eval mode inside the "
+                        "training step (running statistics normalise and do not move; gamma, beta and the conv biases in front still "
+                        "train).  Meant for --pretrained-disp; works with Adam and --sgd, with and without the launch tape")
     p.add_argument("--save-root", default="checkpoints", help="directory under which the run folder is created")
     p.add_argument("--legacy-align-corners", action="store_true",
                    help="photometric warp with F.grid_sample(align_corners=True): the sampling the reference's pinned torch 1.0.1 did at "
@@ -340,8 +344,10 @@ def main(argv=None):
         disp_net.load_state_dict(weights["state_dict"])
     elif not args.monodepth2:
         disp_net.init_weights(use_pretrained_weights=args.pretrained_encoder)
+    if rank == 0 and freeze_bn_warning(args):
+        print(freeze_bn_warning(args))
 
-    hot = list(disp_net._hot_parameters()) if hasattr(disp_net, "_hot_parameters") else [p for p in disp_net.parameters() if p.requires_grad]
+    hot =list(disp_net._hot_parameters()) if hasattr(disp_net, "_hot_parameters") else [p for p in disp_net.parameters() if p.requires_grad]
     if args.train_pose:
         hot += [p for p in pose_exp_net.parameters() if p.requires_grad]
     reducer = None
@@ -434,6 +440,26 @@ def optimizer_state_name(optimizer):
     if hasattr(optimizer, "exp_avg"):
         return "Adam moments start"
     return "the SGD momentum buffer starts"
+
+
+def freeze_batchnorm(net):
+    """Put every BatchNorm module of `net` in eval mode (the loop of the --diff-lr branch, reference train.py:406-411); returns how many.
+    Called after net.train() in every epoch: the network keeps its training outputs and dropout, the engine normalises with the running
+    statistics of each frozen module and leaves its buffers alone."""
+    n = 0
+    for m in net.modules():
+        if m.__class__.__name__.find("BatchNorm") != -1:
+            m.eval()
+            n += 1
+    return n
+
+
+def freeze_bn_warning(args):
+    """The line --freeze-bn prints when there is nothing worth freezing (None: nothing to say)."""
+    if getattr(args, "freeze_bn", False) and not args.pretrained_disp:
+        return ("=> --freeze-bn without --pretrained-disp: the running statistics of a fresh network are mean 0 / variance 1, "
+                "so BatchNorm is frozen at (nearly) the identity")
+    return None
 
 
 def tape_refusal(args, optimizer):
@@ -566,6 +592,8 @@ def train(ctx, loader, disp_net, pose_exp_net, optimizer, epoch_size, n_iter):
         for m in disp_net.modules():
             if m.__class__.__name__.find("BatchNorm") != -1:
                 m.eval()
+    if args.freeze_bn:
+        freeze_batchnorm(disp_net)
     losses, batch_time, data_time = Meter(), Meter(), Meter()
     end = time.time()
     tape = ctx.get("tape")
