@@ -559,6 +559,17 @@ int dn_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, doub
  * at a time under the backward pass) needs nothing further: there is no per-step state besides buf. */
 int dn_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const double* hyper, double weight_decay, double grad_scale,
                     dn_stream_t stream);
+/* The same update with one learning rate per parameter GROUP (torch-style param_groups; train.py --diff-lr), as ONE launch over
+ * elements [lo, hi) of the arena whatever the number of runs inside.  p, g, buf: the arena BASES, 16-byte aligned; lo, hi: multiples of
+ * 4 (arena slices are padded to 4 elements; a slice's padding belongs to its group).  The arena is a sequence of runs of equal group,
+ * described by three DEVICE arrays: seg_end[r] = element offset one past run r (ascending, multiples of 4, seg_end[n_seg-1] >= hi),
+ * seg_group[r] = its group in [0, n_groups), group_lr[grp] = that group's learning rate (double, narrowed to float as dn_sgd_step
+ * narrows lr: every element gets bit for bit what dn_sgd_step gives it with its group's rate).  Any n_seg >= 1.  The rates live on the
+ * device in every mode, so an eager step and a replayed launch tape run the same kernel and both follow a write to group_lr.
+ * 16-byte accesses only, 20 bytes of traffic per element; the run of an element is looked up per wave through the scalar cache. */
+int dn_sgd_step_groups(float* p, const float* g, float* buf, int64_t lo, int64_t hi, const int64_t* seg_end, const int32_t* seg_group,
+                       int32_t n_seg, const double* group_lr, int32_t n_groups, double momentum, double weight_decay, double grad_scale,
+                       dn_stream_t stream);
 int dn_fill(float* p, float value, int64_t n, dn_stream_t stream);
 /* dst[i] = src[i], n floats (the owned copy engine.seed_grad takes of a gradient autograd hands over; on the launch tape like every
  * other kernel of this library, which a framework-side copy would not be). */

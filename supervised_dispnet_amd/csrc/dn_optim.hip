@@ -131,6 +131,74 @@ __global__ void __launch_bounds__(kThreads) sgd_dev_kernel(float* __restrict__ p
   sgd_range(p, g, buf, n, lr, momentum, weight_decay, grad_scale);
 }
 
+// Per-group learning rates over one arena range (FusedSGD with parameter groups: train.py --diff-lr).  The arena is a sequence of RUNS of
+// equal group: seg_end[r] is the element offset one past run r (ascending, multiples of 4, the last one >= hi), seg_group[r] its group,
+// group_lr[g] that group's learning rate as a double, all on the device, so the eager and the taped step are the same launch and a
+// replayed tape follows a scheduler that writes group_lr.  Elements [lo, hi) of the arena, 16-byte accesses only (every offset is a
+// multiple of 4 and the bases are 16-byte aligned), the same grid-stride walk as sgd_range: 20 bytes of traffic per element.
+//
+// The lookup stays off the memory path by being done per WAVE, not per lane.  A wave's 64 float4 are 256 consecutive elements; the run of
+// their first element is a binary search whose every operand is wave-uniform (blockIdx, the loop counter, readfirstlane of the wave
+// number), so the table is read with scalar loads through the scalar cache and the three 16-byte loads of the iteration, issued before
+// it, are in flight meanwhile.  If that run also holds the wave's last element -- always, but for the few waves that straddle a slice
+// boundary -- every lane takes the one rate.  A straddling wave searches per lane, but only between the runs of its first and last element.
+// Any n_seg >= 1: nothing is staged, so nothing is capped.
+__device__ __forceinline__ int sgd_run_of(const long long* __restrict__ seg_end, int first, int last, const long long e) {
+  while (first < last) {                       // the smallest r in [first, last] with seg_end[r] > e; `last` when there is none
+    const int mid = (first + last) >> 1;
+    if (seg_end[mid] > e)
+      last = mid;
+    else
+      first = mid + 1;
+  }
+  return first;
+}
+
+// The rate of run r, narrowed as sgd_dev_kernel narrows hyper[0].  A table that breaks its contract reads a wrong rate, never out of bounds.
+__device__ __forceinline__ float sgd_group_lr(const int* __restrict__ seg_group, const double* __restrict__ group_lr, const int n_groups,
+                                              const int r) {
+  const int grp = seg_group[r];
+  return (float)group_lr[grp < 0 ? 0 : (grp >= n_groups ? n_groups - 1 : grp)];
+}
+
+__global__ void __launch_bounds__(kThreads) sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                              const long long lo, const long long hi,
+                                                              const long long* __restrict__ seg_end, const int* __restrict__ seg_group,
+                                                              const int n_seg, const double* __restrict__ group_lr, const int n_groups,
+                                                              const float momentum, const float weight_decay, const float grad_scale) {
+  const long long v0 = lo >> 2, nvec = (hi - lo) >> 2, stride = (long long)gridDim.x * kThreads;
+  float4* __restrict__ p4 = reinterpret_cast<float4*>(p) + v0;
+  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g) + v0;
+  float4* __restrict__ b4 = reinterpret_cast<float4*>(buf) + v0;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  for (long long base = blockIdx.x * (long long)kThreads + wave * 64; base < nvec; base += stride) {        // wave-uniform
+    const long long i = base + (threadIdx.x & 63);
+    const bool live = i < nvec;
+    float4 pv, bv, gv;
+    if (live) {
+      pv = p4[i];
+      bv = b4[i];
+      gv = g4[i];
+    }
+    const long long wlast = base + 63 < nvec ? base + 63 : nvec - 1;
+    const int r0 = sgd_run_of(seg_end, 0, n_seg - 1, (v0 + base) << 2);
+    float lr = sgd_group_lr(seg_group, group_lr, n_groups, r0);      // (wave-uniform: scalar loads again)
+    if (seg_end[r0] <= ((v0 + wlast) << 2)) {                        // this wave straddles runs: each lane finds its own
+      const int r1 = sgd_run_of(seg_end, r0, n_seg - 1, (v0 + wlast) << 2);
+      const int r = sgd_run_of(seg_end, r0, r1, (v0 + (live ? i : base)) << 2);
+      if (r != r0) lr = sgd_group_lr(seg_group, group_lr, n_groups, r);
+    }
+    if (live) {
+      sgd_update(pv.x, gv.x, bv.x, lr, momentum, weight_decay, grad_scale);
+      sgd_update(pv.y, gv.y, bv.y, lr, momentum, weight_decay, grad_scale);
+      sgd_update(pv.z, gv.z, bv.z, lr, momentum, weight_decay, grad_scale);
+      sgd_update(pv.w, gv.w, bv.w, lr, momentum, weight_decay, grad_scale);
+      b4[i] = bv;
+      p4[i] = pv;
+    }
+  }
+}
+
 }  // namespace dn
 
 using namespace dn;
@@ -179,6 +247,19 @@ int dn_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const doubl
   DN_LAUNCH(sgd_dev_kernel, dim3(ew_blocks((n + 3) / 4)), dim3(kThreads), 0, as_stream(stream), p, g, buf, (long long)n, hyper,
                      (float)weight_decay, (float)grad_scale);
   return check_launch("sgd_dev_kernel");
+}
+
+int dn_sgd_step_groups(float* p, const float* g, float* buf, int64_t lo, int64_t hi, const int64_t* seg_end, const int32_t* seg_group,
+                       int32_t n_seg, const double* group_lr, int32_t n_groups, double momentum, double weight_decay, double grad_scale,
+                       dn_stream_t stream) {
+  const uintptr_t bases = (uintptr_t)p | (uintptr_t)g | (uintptr_t)buf;
+  DN_REQUIRE(p && g && buf && seg_end && seg_group && group_lr && lo >= 0 && hi > lo && n_seg >= 1 && n_groups >= 1 &&
+                 (bases & 15) == 0 && ((lo | hi) & 3) == 0,
+             DN_ERR_BAD_ARG, "dn_sgd_step_groups: bad argument");
+  DN_LAUNCH(sgd_groups_kernel, dim3(ew_blocks((hi - lo) / 4)), dim3(kThreads), 0, as_stream(stream), p, g, buf, (long long)lo, (long long)hi,
+            reinterpret_cast<const long long*>(seg_end), reinterpret_cast<const int*>(seg_group), (int)n_seg, group_lr, (int)n_groups,
+            (float)momentum, (float)weight_decay, (float)grad_scale);
+  return check_launch("sgd_groups_kernel");
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from .. import engine
 from .._lib import ACT_SIGMOID_AFFINE
-from ._common import run_net
+from ._common import EncoderLrGroups, run_net
 from .Disp_res_50 import run_residual_block
 
 affine_par = True
@@ -83,7 +83,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
 
-class _ASPPDepth(nn.Module):
+class _ASPPDepth(EncoderLrGroups, nn.Module):
     _counts = (3, 4, 23, 3)
     _tv = "resnet101"
 
@@ -116,6 +116,10 @@ class _ASPPDepth(nn.Module):
     def _hot_parameters(self):
         """The trainable ones: the frozen BatchNorm pairs take no gradient (their layers still compute one for their inputs)."""
         return [q for q in self.parameters() if q.requires_grad]
+
+    def _pretrainable_encoder(self):
+        S = self.Scale
+        return [S.conv1, S.bn1, S.layer1, S.layer2, S.layer3, S.layer4]     # the torchvision ResNet's stem and stages; layer5 is the ASPP head
 
     def _grad_production_order(self):
         S = self.Scale

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from .. import engine
 from .._lib import ACT_LEAKY, ACT_RELU, ACT_SIGMOID_AFFINE
-from ._common import run_net, xavier_init_like_reference
+from ._common import EncoderLrGroups, run_net, xavier_init_like_reference
 from .Disp_res_50 import Bottleneck, conv1x1, predict_disp, residual_block_params_backward_order, run_residual_block
 
 
@@ -26,7 +26,7 @@ def _upconv(in_planes, out_planes, leaky):
                          nn.LeakyReLU(0.1) if leaky else nn.ReLU(inplace=True))
 
 
-class Disp_res(nn.Module):
+class Disp_res(EncoderLrGroups, nn.Module):
     _layer3_blocks = 6
     _leaky = True                 # models/Disp_res.py:17-39: conv()/upconv() default to leaky=True
     _pretrained_url = 'https://download.pytorch.org/models/resnet50-19c8e357.pth'
@@ -101,6 +101,9 @@ class Disp_res(nn.Module):
     def _hot_parameters(self):
         skip = {id(self.bn1.weight), id(self.bn1.bias)}
         return [p for p in self.parameters() if id(p) not in skip]
+
+    def _pretrainable_encoder(self):
+        return [self.conv1, self.bn1, self.layer1, self.layer2, self.layer3, self.layer4]     # the torchvision ResNet's stem and stages
 
     def _grad_production_order(self):
         order = []

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from .. import engine
 from .._lib import ACT_LEAKY, ACT_RELU, ACT_SIGMOID_AFFINE
-from ._common import run_net, xavier_init_like_reference
+from ._common import EncoderLrGroups, run_net, xavier_init_like_reference
 
 
 def predict_disp(in_planes):
@@ -108,7 +108,7 @@ def residual_block_params_backward_order(blk):
     return out
 
 
-class Disp_res_50(nn.Module):
+class Disp_res_50(EncoderLrGroups, nn.Module):
     # what Disp_res_18 (reference models/Disp_res_18.py:50-135: BasicBlock, expansion written out as 1) changes
     _block, _expansion, _counts = Bottleneck, 4, (3, 4, 6, 3)
     _pretrained_url = 'https://download.pytorch.org/models/resnet50-19c8e357.pth'
@@ -183,6 +183,9 @@ class Disp_res_50(nn.Module):
         """Everything except bn1's affine pair, which the reference's forward never uses (:141-145)."""
         skip = {id(self.bn1.weight), id(self.bn1.bias)}
         return [p for p in self.parameters() if id(p) not in skip]
+
+    def _pretrainable_encoder(self):
+        return [self.conv1, self.bn1, self.layer1, self.layer2, self.layer3, self.layer4]     # the torchvision ResNet's stem and stages
 
     def _grad_production_order(self):
         order = []

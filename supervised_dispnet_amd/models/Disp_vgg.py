@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from .. import engine
 from .._lib import ACT_RELU, ACT_SIGMOID_AFFINE
-from ._common import run_net, xavier_init_like_reference
+from ._common import EncoderLrGroups, run_net, xavier_init_like_reference
 
 _STAGE_CFG = ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512))
 
@@ -37,7 +37,7 @@ def _encoder_stage(cfg, c_in):
     return nn.Sequential(*layers)
 
 
-class _VggDispBase(nn.Module):
+class _VggDispBase(EncoderLrGroups, nn.Module):
     """Decoder + schedule shared by the two mirrors; subclasses provide `_encoder_convs()` -> five lists of nn.Conv2d."""
 
     def _build_decoder(self):
@@ -52,6 +52,9 @@ class _VggDispBase(nn.Module):
     def forward(self, x):
         outs = run_net(self, x)
         return outs if self.training else outs[0]
+
+    def _pretrainable_encoder(self):
+        return [m for stage in self._encoder_convs() for m in stage]      # the vgg16 trunk's 13 convolutions
 
     def _grad_production_order(self):
         order = []

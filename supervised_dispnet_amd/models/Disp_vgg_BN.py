@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from .. import engine
 from .._lib import ACT_LEAKY, ACT_SIGMOID_AFFINE
-from ._common import VGG16BNContainer, VGG_STAGES, run_net, xavier_init_like_reference
+from ._common import EncoderLrGroups, VGG16BNContainer, VGG_STAGES, run_net, xavier_init_like_reference
 
 
 def _upconv(c_in, c_out):
@@ -26,7 +26,7 @@ def _predict_disp(c_in):
     return nn.Sequential(nn.Conv2d(c_in, 1, kernel_size=3, padding=1), nn.Sigmoid())
 
 
-class Disp_vgg_BN(nn.Module):
+class Disp_vgg_BN(EncoderLrGroups, nn.Module):
     def __init__(self, datasets='kitti', with_classifier=True):
         super(Disp_vgg_BN, self).__init__()
         self.only_train_dec = False
@@ -70,6 +70,9 @@ class Disp_vgg_BN(nn.Module):
         for name, p in self.named_parameters():
             if ".classifier." not in name:
                 yield p
+
+    def _pretrainable_encoder(self):
+        return [self.features.features]          # the vgg16_bn trunk, without the unused classifier
 
     def _grad_production_order(self):
         """Parameters in the order backward writes their gradients (decoder first, encoder stage 5 -> 1): the arena and

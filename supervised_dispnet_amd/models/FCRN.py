@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from .. import engine
 from .._lib import ACT_SIGMOID_AFFINE
-from ._common import run_net
+from ._common import EncoderLrGroups, run_net
 from .Disp_res_50 import Bottleneck, conv1x1, run_residual_block, residual_block_params_backward_order
 
 
@@ -62,7 +62,7 @@ def upproject_params_backward_order(up):
     return out
 
 
-class FCRN(nn.Module):
+class FCRN(EncoderLrGroups, nn.Module):
     def __init__(self, datasets='kitti'):
         super(FCRN, self).__init__()
         if datasets == 'kitti':
@@ -130,6 +130,9 @@ class FCRN(nn.Module):
     # ------------------------------------------------------------------ engine side
     def _hot_parameters(self):
         return list(self.parameters())
+
+    def _pretrainable_encoder(self):
+        return [self.conv1, self.bn1, self.layer1, self.layer2, self.layer3, self.layer4]     # the torchvision ResNet's stem and stages
 
     def _grad_production_order(self):
         order = [self.conv3.bias, self.conv3.weight]

@@ -51,6 +51,26 @@ class VGG16Container(nn.Module):
                                             nn.Linear(4096, 4096), nn.ReLU(True), nn.Dropout(), nn.Linear(4096, 1000))
 
 
+class EncoderLrGroups(object):
+    """get_1x_lr_params() / get_10x_lr_params() of the reference's models/DORN.py:222-236 (what train.py --diff-lr builds its two
+    parameter groups from) for a network with a pretrainable encoder.  1x: the trainable hot parameters of the modules
+    `_pretrainable_encoder()` returns (what an ImageNet checkpoint fills); 10x: every other trainable hot parameter.  The two are
+    disjoint and together the trainable part of `_hot_parameters()`, each in that order."""
+
+    def _lr_split(self):
+        encoder = {id(p) for m in self._pretrainable_encoder() for p in m.parameters()}
+        hot = [p for p in self._hot_parameters() if p.requires_grad]
+        return [p for p in hot if id(p) in encoder], [p for p in hot if id(p) not in encoder]
+
+    def get_1x_lr_params(self):
+        for p in self._lr_split()[0]:
+            yield p
+
+    def get_10x_lr_params(self):
+        for p in self._lr_split()[1]:
+            yield p
+
+
 def xavier_init_like_reference(module):
     """init_weights() of the reference nets: xavier_uniform_ on every Conv2d / ConvTranspose2d / Linear weight, zero
     bias; the BatchNorm branch is unreachable there (models/Disp_vgg_BN.py:116-120) so BN keeps gamma=1, beta=0."""

@@ -3,10 +3,10 @@ whole thing runs as ONE engine tape (features never leave NHWC, no autograd hand
 pair falls back to plain composition of the two modules."""
 import torch.nn as nn
 
-from ._common import run_net
+from ._common import EncoderLrGroups, run_net
 
 
-class monodepth2(nn.Module):
+class monodepth2(EncoderLrGroups, nn.Module):
     def __init__(self, encoder, decoder):
         super(monodepth2, self).__init__()
         self.encoder = encoder
@@ -23,6 +23,9 @@ class monodepth2(nn.Module):
 
     def _hot_parameters(self):
         return list(self.encoder._hot_parameters()) + list(self.decoder._hot_parameters())
+
+    def _pretrainable_encoder(self):
+        return [self.encoder]
 
     def _hip_forward(self, tape, sink, x):
         feats = self.encoder._hip_features(tape, sink, x)

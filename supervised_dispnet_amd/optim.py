@@ -7,20 +7,69 @@ FusedAdam (HIP): one `dn_adam_step` launch over the whole arena; numerics follow
 lerp / addcmul updates, denom = sqrt(v)/sqrt(1-b2^t) + eps, step_size = lr/(1-b1^t); grad * (1/world) folded in.
 FusedSGD (HIP): the same surface over the same arena with one `dn_sgd_step` launch; numerics follow torch.optim.SGD with momentum
 (dampening 0, nesterov off): buf = momentum*buf + (g + wd*p), p -= lr*buf, the buffer starting as zeros.
+Parameter groups (torch-style `[{"params": ..., "lr": ...}, ...]`; only lr may differ): the arena keeps its production order, records each
+slice's group and the runs of equal group, and FusedSGD updates any range with one `dn_sgd_step_groups` launch.
 """
 import torch
 
 from . import _lib, engine
 
 
+def split_param_groups(params):
+    """What the arena and the optimizers are constructed from -- a flat parameter list or torch-style groups -- as (the parameters in
+    construction order, the group of each, one dict of the options besides "params" per group).  Construction order is what a
+    torch.optim state dict indexes.  Only "lr" may differ between groups: a parameter listed twice, or another key set to two different
+    values, is a ValueError.  Pure bookkeeping, no device."""
+    params = list(params)
+    if not params or not isinstance(params[0], dict):
+        return params, [0] * len(params), [{}]
+    listed, group_of, options, seen = [], [], [], set()
+    for gi, g in enumerate(params):
+        if not isinstance(g, dict) or "params" not in g:
+            raise ValueError("parameter group %d is not a dict with a 'params' entry" % gi)
+        ps = [g["params"]] if isinstance(g["params"], torch.Tensor) else list(g["params"])
+        for p in ps:
+            if id(p) in seen:
+                raise ValueError("a parameter of group %d appears in more than one parameter group (or twice in one)" % gi)
+            seen.add(id(p))
+        listed += ps
+        group_of += [gi] * len(ps)
+        options.append({k: v for k, v in g.items() if k != "params"})
+    for key in sorted({k for o in options for k in o if k != "lr"}):
+        values = [o[key] for o in options if key in o]
+        if any(v != values[0] for v in values):
+            raise ValueError("parameter groups set %s to %s: only lr may differ between the groups of one arena" % (key, values))
+    return listed, group_of, options
+
+
+def group_runs(offsets, total, group_of):
+    """The runs of equal group over an arena: [(end offset in elements, group)], ends ascending, the last one `total`.  A slice reaches
+    to the next slice's offset, so its padding belongs to its group."""
+    runs = []
+    for i, g in enumerate(group_of):
+        end = offsets[i + 1] if i + 1 < len(offsets) else total
+        if runs and runs[-1][1] == g:
+            runs[-1] = (end, g)
+        else:
+            runs.append((end, g))
+    return runs
+
+
 class ParamArena(object):
     def __init__(self, params, production_order=None):
-        params = [p for p in params if p.requires_grad]
+        self.listed, listed_group, self.group_options = split_param_groups(params)
+        self.listed_group = listed_group                 # group of listed[i]; listed = construction order, frozen parameters included
+        group = {id(p): g for p, g in zip(self.listed, listed_group)}
+        params = [p for p in self.listed if p.requires_grad]
         if not params:
             raise ValueError("ParamArena got no trainable parameters")
         if production_order is not None:
             rank = {id(p): i for i, p in enumerate(production_order)}
             params = sorted(params, key=lambda p: rank.get(id(p), len(rank)))
+            if len(self.group_options) > 1:
+                missed = sum(1 for p in production_order if p.requires_grad and id(p) not in group)
+                if missed:
+                    raise ValueError("the parameter groups miss %d trainable parameter(s) of the production order" % missed)
         self.params = params
         dev = params[0].device
         offs, total = [], 0
@@ -28,6 +77,9 @@ class ParamArena(object):
             offs.append(total)
             total += (p.numel() + 3) // 4 * 4        # 16-byte aligned slices
         self.numel, self.offsets = total, offs
+        self.n_groups = len(self.group_options)
+        self.group_of = [group[id(p)] for p in params]       # per slice, in arena (= gradient production) order
+        self.runs = group_runs(offs, total, self.group_of)
         self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
         with torch.no_grad():
@@ -84,8 +136,14 @@ class _ArenaOptimizer(object):
 
 class FusedAdam(_ArenaOptimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, production_order=None):
-        self.arena = params if isinstance(params, ParamArena) else ParamArena(list(params), production_order)
+        if not isinstance(params, ParamArena):
+            params = list(params)
+        if (params.n_groups if isinstance(params, ParamArena) else len(split_param_groups(params)[2])) > 1:
+            # (the reference's grouped recipe, --diff-lr, is SGD; there is no grouped Adam kernel and nothing falls back to a loop of launches)
+            raise ValueError("FusedAdam takes one parameter group; per-group learning rates are FusedSGD's (dn_sgd_step_groups)")
+        self.arena = params if isinstance(params, ParamArena) else ParamArena(params, production_order)
         engine.require_cuda(self.arena.flat_p, "parameters")
+        lr = self.arena.group_options[0].get("lr", lr)
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.step_count = 0
         self.exp_avg = torch.zeros_like(self.arena.flat_p)
@@ -206,28 +264,71 @@ def flat_momentum_from_torch_sgd(sd, params, arena):
     return flat
 
 
+def grouped_state(param_groups, listed_group):
+    """state_dict()["param_groups"] of a grouped optimizer, as torch writes it: each group's hyper-parameters plus "params", the indices of
+    its parameters in the construction-order list (listed_group[i] = the group of parameter i)."""
+    return [dict({k: v for k, v in g.items() if k != "params"}, params=[i for i, gg in enumerate(listed_group) if gg == gi])
+            for gi, g in enumerate(param_groups)]
+
+
+def require_same_grouping(sd, sizes):
+    """ValueError unless the state dict's param_groups list as many parameters, group by group, as `sizes`."""
+    got = [len(g["params"]) if "params" in g else None for g in sd.get("param_groups", [])]
+    if got != list(sizes):
+        raise ValueError("optimizer state for parameter groups of sizes %s, this optimizer has groups of sizes %s" % (got, list(sizes)))
+
+
 class FusedSGD(_ArenaOptimizer):
     """torch.optim.SGD with momentum (dampening 0, nesterov off) as one dn_sgd_step launch over the arena: FusedAdam's surface, so
     distributed.GradReducer, graph.TapedStep / GraphedStep and train.py take either.  The momentum buffer starts as zeros, which is the
     gradient copy torch's first step makes (momentum*0 + g), so there is no step counter: any range of the arena is one launch and
     apply_range's `tick` has nothing to do."""
 
-    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, production_order=None):
+    def __init__(self, params, lr=None, momentum=0.0, weight_decay=0.0, production_order=None):
+        hyper = {"momentum": float(momentum), "weight_decay": float(weight_decay), "dampening": 0, "nesterov": False}
         if isinstance(params, ParamArena):
-            self.arena, self._listed = params, list(params.params)
+            options = params.group_options
         else:
-            self._listed = list(params)       # construction order: the index of a torch.optim.SGD state dict
-            self.arena = ParamArena(self._listed, production_order)
+            params = list(params)
+            options = split_param_groups(params)[2]
+        for gi, o in enumerate(options):          # (before the arena re-points a single parameter)
+            for k, v in o.items():
+                if k != "lr" and (k not in hyper or v != hyper[k]):
+                    raise ValueError("FusedSGD: parameter group %d sets %s=%r, the optimizer has %r: only lr may differ between groups"
+                                     % (gi, k, v, hyper.get(k, "no such option")))
+            if "lr" not in o and lr is None:
+                raise ValueError("FusedSGD: no learning rate for parameter group %d" % gi)
+        if isinstance(params, ParamArena):
+            self.arena = params
+            # (one group: a torch.optim.SGD state dict indexes the arena's own list, as it always has for a ready-made arena)
+            self._listed = list(params.params) if params.n_groups == 1 else list(params.listed)
+        else:
+            self.arena = ParamArena(params, production_order)
+            self._listed = list(self.arena.listed)       # construction order: the index of a torch.optim.SGD state dict
         engine.require_cuda(self.arena.flat_p, "parameters")
+        a = self.arena
         self.weight_decay = float(weight_decay)
-        self.momentum_buffer = torch.zeros_like(self.arena.flat_p)
-        self.param_groups = [{"params": self.arena.params, "lr": float(lr), "momentum": float(momentum), "weight_decay": self.weight_decay,
-                              "dampening": 0, "nesterov": False}]
+        self.momentum_buffer = torch.zeros_like(a.flat_p)
+        rates = [float(o.get("lr", lr)) for o in options]
         self._dev = None          # capturable(): device-resident (lr, momentum) for a captured or taped step
+        self._table = None        # several groups: the run table and the rates, on the device in every mode (dn_sgd_step_groups)
         self._overlap = None
+        if a.n_groups == 1:
+            self.param_groups = [{"params": a.params, "lr": rates[0], "momentum": float(momentum), "weight_decay": self.weight_decay,
+                                  "dampening": 0, "nesterov": False}]
+            return
+        self.param_groups = [{"params": [p for p, g in zip(a.listed, a.listed_group) if g == gi], "lr": rates[gi], "momentum": float(momentum),
+                              "weight_decay": self.weight_decay, "dampening": 0, "nesterov": False} for gi in range(a.n_groups)]
+        dev = a.flat_p.device
+        self._table = {"seg_end": torch.tensor([e for e, _ in a.runs], dtype=torch.int64, device=dev),
+                       "seg_group": torch.tensor([g for _, g in a.runs], dtype=torch.int32, device=dev),
+                       "lr": torch.tensor(rates, dtype=torch.float64, device=dev), "host": list(rates)}
 
     def capturable(self, on=True):
-        """Keep (lr, momentum) on the DEVICE (dn_sgd_step_dev) so that a captured step follows a scheduler: set_lr() writes the value."""
+        """Keep (lr, momentum) on the DEVICE (dn_sgd_step_dev) so that a captured step follows a scheduler: set_lr() writes the value.
+        With several groups the rates are on the device in every mode and there is nothing to move."""
+        if self._table is not None:
+            return self
         if on and self._dev is None:
             g = self.param_groups[0]
             self._dev = {"hyper": torch.tensor([float(g["lr"]), float(g["momentum"])], dtype=torch.float64, device=self.arena.flat_p.device),
@@ -236,18 +337,32 @@ class FusedSGD(_ArenaOptimizer):
             self._dev = None
         return self
 
-    def set_lr(self, lr):
-        self.param_groups[0]["lr"] = float(lr)
-        if self._dev is not None and self._dev["lr"] != float(lr):
+    def set_lr(self, lr, group=0):
+        self.param_groups[group]["lr"] = float(lr)
+        if self._table is not None:
+            if self._table["host"][group] != float(lr):
+                self._table["lr"][group:group + 1].fill_(float(lr))
+                self._table["host"][group] = float(lr)
+        elif self._dev is not None and self._dev["lr"] != float(lr):
             self._dev["hyper"][0:1].fill_(float(lr))
             self._dev["lr"] = float(lr)
 
     @torch.no_grad()
     def apply_range(self, lo, hi, grad_scale=1.0, tick=True):
         """SGD update of arena elements [lo, hi) on the current stream (engine.stream_scope).  `tick` is FusedAdam's once-per-step
-        advance of its counter; SGD has no per-step state, so it is accepted and unused."""
+        advance of its counter; SGD has no per-step state, so it is accepted and unused.  Several groups: one dn_sgd_step_groups launch
+        over the arena bases and the range, whatever runs the range cuts through."""
         a, g = self.arena, self.param_groups[0]
         n = hi - lo
+        if self._table is not None:
+            t = self._table
+            for gi, grp in enumerate(self.param_groups):
+                if t["host"][gi] != float(grp["lr"]):
+                    self.set_lr(grp["lr"], gi)
+            engine.hbm_call("dn::sgd_groups_kernel", n * 20, "dn_sgd_step_groups", a.flat_p.data_ptr(), a.flat_g.data_ptr(),
+                            self.momentum_buffer.data_ptr(), lo, hi, t["seg_end"].data_ptr(), t["seg_group"].data_ptr(), len(a.runs),
+                            t["lr"].data_ptr(), a.n_groups, float(g["momentum"]), self.weight_decay, float(grad_scale), engine._stream())
+            return
         ptr = lambda t: t.data_ptr() + 4 * lo
         if self._dev is not None:
             if self._dev["lr"] != float(g["lr"]):
@@ -272,11 +387,17 @@ class FusedSGD(_ArenaOptimizer):
         return [self.arena.flat_p, self.momentum_buffer]
 
     def state_dict(self):
-        return {"momentum_buffer": self.momentum_buffer.clone(),
-                "param_groups": [{k: v for k, v in self.param_groups[0].items() if k != "params"}]}
+        if len(self.param_groups) == 1:
+            groups = [{k: v for k, v in self.param_groups[0].items() if k != "params"}]
+        else:
+            groups = grouped_state(self.param_groups, self.arena.listed_group)
+        return {"momentum_buffer": self.momentum_buffer.clone(), "param_groups": groups}
 
     def load_state_dict(self, sd):
-        """This class's own form, or a torch.optim.SGD state dict over the parameter list this optimizer was constructed from."""
+        """This class's own form, or a torch.optim.SGD state dict over the parameter list (or groups) this optimizer was constructed from.
+        The state is the momentum buffer; the rates stay what the constructor or set_lr made them."""
+        if len(self.param_groups) > 1 or len(sd.get("param_groups", [])) > 1:
+            require_same_grouping(sd, [len(g["params"]) for g in self.param_groups] if len(self.param_groups) > 1 else [len(self._listed)])
         if "momentum_buffer" in sd:
             flat = sd["momentum_buffer"]
             if flat.numel() != self.arena.numel:

@@ -1,6 +1,8 @@
 """Kernel time of the fused optimizers over the Disp_vgg_BN arena: one dn_sgd_step next to one dn_adam_step, HIP events around
-back-to-back launches on resident data, alternating the two between repeats.  Both are HBM-bound passes; the algorithmic traffic is
-20 bytes per element for SGD (read p, g, buf; write buf, p) and 28 for Adam (read p, g, m, v; write m, v, p).
+back-to-back launches on resident data, alternating between repeats.  All are HBM-bound passes; the algorithmic traffic is
+20 bytes per element for SGD (read p, g, buf; write buf, p) and 28 for Adam (read p, g, m, v; write m, v, p).  Next to the ungrouped
+SGD update, on the same arena and in the same alternation, the grouped one (dn_sgd_step_groups): "sgd_groups_split" with the network's
+own 1x / 10x split (two runs), "sgd_groups_alternating" with the group changing on every slice (the most runs this arena can have).
 
     python tools/optimizer_bench.py [--launches 200] [--repeats 7] [--warmup 20]
 
@@ -29,7 +31,8 @@ def main(argv=None):
         raise SystemExit("optimizer_bench: needs an MI355X (there is no CPU path to time)")
     import bench
     import supervised_dispnet_amd.models as models
-    from supervised_dispnet_amd.optim import FusedAdam, FusedSGD, ParamArena
+    from supervised_dispnet_amd import _lib, engine
+    from supervised_dispnet_amd.optim import FusedAdam, FusedSGD, ParamArena, group_runs
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     net = models.Disp_vgg_BN(datasets="kitti", with_classifier=False)
@@ -38,6 +41,28 @@ def main(argv=None):
     arena = ParamArena(list(net._hot_parameters()), net._grad_production_order())
     arena.flat_g.normal_(0, 1e-3)
     opts = {"adam": (FusedAdam(arena, lr=1e-6), 28), "sgd": (FusedSGD(arena, lr=1e-6, momentum=0.9, weight_decay=5e-4), 20)}
+    sgd = opts["sgd"][0]
+    encoder = {id(p) for p in net.get_1x_lr_params()}
+    tables = {"sgd_groups_split": [0 if id(p) in encoder else 1 for p in arena.params],
+              "sgd_groups_alternating": [i % 2 for i in range(len(arena.params))]}
+    rates = torch.tensor([1e-6, 1e-5], dtype=torch.float64, device=dev)
+    runs_of = {}
+
+    class Grouped(object):
+        """dn_sgd_step_groups over the whole arena with one run table, on the ungrouped optimizer's buffers."""
+
+        def __init__(self, group_of):
+            self.runs = group_runs(arena.offsets, arena.numel, group_of)
+            self.seg_end = torch.tensor([e for e, _ in self.runs], dtype=torch.int64, device=dev)
+            self.seg_group = torch.tensor([g for _, g in self.runs], dtype=torch.int32, device=dev)
+
+        def step(self):
+            _lib.call("dn_sgd_step_groups", arena.flat_p.data_ptr(), arena.flat_g.data_ptr(), sgd.momentum_buffer.data_ptr(), 0, arena.numel,
+                      self.seg_end.data_ptr(), self.seg_group.data_ptr(), len(self.runs), rates.data_ptr(), 2, 0.9, 5e-4, 1.0, engine._stream())
+
+    for name, group_of in tables.items():
+        opts[name] = (Grouped(group_of), 20)
+        runs_of[name] = len(opts[name][0].runs)
     times = {k: [] for k in opts}
     for opt, _ in opts.values():
         for _ in range(args.warmup):
@@ -58,6 +83,9 @@ def main(argv=None):
         med = statistics.median(times[name])
         out[name] = {"us_median": round(med, 2), "us_min": round(min(times[name]), 2), "us_max": round(max(times[name]), 2),
                      "bytes_per_element": bytes_per, "GBps_median": round(arena.numel * bytes_per / med / 1e3, 1)}
+        if name in runs_of:
+            out[name]["runs"] = runs_of[name]
+            out[name]["median_over_sgd"] = round(med / statistics.median(times["sgd"]), 4)
     print(json.dumps(out))
 
 

@@ -49,7 +49,8 @@ def build_parser():
     p.add_argument("--pretrained-encoder", action="store_true", help="use imagenet pretrained parameter.")
     p.add_argument("--loss", default="Multi_L1", type=str, help="loss type")
     p.add_argument("--ordinal-c", default=80, type=int, metavar="N", help="DORN loss channel number")
-    p.add_argument("--diff-lr", action="store_true", help="use different learning rate for encoder and decoder")
+    p.add_argument("--diff-lr", action="store_true", help="use different learning rate for encoder and decoder: SGD with momentum (FusedSGD "
+                   "with two parameter groups), the pretrainable encoder at --lr, everything else at 10 x --lr, BatchNorm frozen")
     p.add_argument("--sgd", action="store_true", help="use sgd optimizer, if not then adam")
     p.add_argument("--record", action="store_true", help="save every epoch checkpoints")
     p.add_argument("--unsupervised", action="store_true", help="to have unsupervised loss")
@@ -96,7 +97,7 @@ def build_parser():
     p.add_argument("--img-width", type=int, default=416, help="synthetic image width")
     p.add_argument("--train-pose", action="store_true", help="also optimise PoseExpNet (the reference never does, appendix C-3)")
     p.add_argument("--tape", dest="tape", action="store_true", default=None,
-                   help="supervised per-sample / multi-scale losses with a fused optimizer (not --diff-lr): record the launches of one training step and re-issue "
+                   help="supervised per-sample / multi-scale losses with a fused optimizer (Adam, --sgd or --diff-lr): record the launches of one training step and re-issue "
                         "them with one call per step (supervised_dispnet_amd.graph.TapedStep); the second batch checks the replay against "
                         "the eager step bit for bit, a mismatch falls back to eager launches with a message.  This is the DEFAULT wherever the "
                         "setting is eligible (at the reference's own -b4 the eager step is host-bound: 5.0 ms against 3.5 taped); an "
@@ -351,17 +352,20 @@ def main(argv=None):
     if args.train_pose:
         hot += [p for p in pose_exp_net.parameters() if p.requires_grad]
     reducer = None
-    plain_params = None          # torch.optim path (--diff-lr): gradients live in p.grad and are exchanged per step
     order = disp_net._grad_production_order() if hasattr(disp_net, "_grad_production_order") else None
     if args.diff_lr:
         if not hasattr(disp_net, "get_1x_lr_params"):
             # the reference's only network with these methods is models/DORN.py:222-236 (train.py:306-312 calls them unconditionally and
-            # dies with AttributeError for every other --network); the full DORN model is outside SURVEY.md section 8
+            # dies with AttributeError for every other --network); here every network with a pretrainable encoder has them
+            # (models/_common.py: EncoderLrGroups), DispNetS has no such encoder
             raise SystemExit("--diff-lr needs a network with get_1x_lr_params() / get_10x_lr_params() (reference: models.DORN only)")
-        # (not on the arena: the two groups interleave in production order, so FusedSGD would need a per-slice learning-rate table)
-        groups = [{"params": disp_net.get_1x_lr_params(), "lr": args.lr}, {"params": disp_net.get_10x_lr_params(), "lr": args.lr * 10}]
-        optimizer = torch.optim.SGD(groups, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
-        plain_params = [p for g in optimizer.param_groups for p in g["params"]]
+        # SGD with momentum, the encoder at --lr and everything else at 10 x --lr (reference train.py:306-312), on the arena: the two groups
+        # interleave in gradient production order and FusedSGD looks the rate of a slice up in the kernel
+        groups = diff_lr_groups(disp_net, args.lr)
+        optimizer = FusedSGD(groups, momentum=args.momentum, weight_decay=args.weight_decay, production_order=order)
+        if rank == 0:
+            print("=> setting sgd solver with two learning rates: {} parameters at {:g} (encoder), {} at {:g}".format(
+                len(groups[0]["params"]), groups[0]["lr"], len(groups[1]["params"]), groups[1]["lr"]))
     elif args.sgd:
         if rank == 0:
             print("=> setting sgd solver")
@@ -370,7 +374,7 @@ def main(argv=None):
         if rank == 0:
             print("=> setting adam solver")
         optimizer = FusedAdam(hot, lr=args.lr, betas=(args.momentum, args.beta), weight_decay=args.weight_decay, production_order=order)
-    if plain_params is None and world > 1:
+    if world > 1:
         reducer = GradReducer(optimizer.arena)
         engine.GradSink.reducer = reducer
     if weights is not None and "optimizer" in weights and not args.monodepth2:
@@ -385,8 +389,7 @@ def main(argv=None):
         with open(os.path.join(save_path, args.log_full), "w") as f:
             csv.writer(f, delimiter="\t").writerow(["train_loss", "photo_loss", "explainability_loss", "smooth_loss"])
 
-    ctx = dict(args=args, device=device, LF=LF, U=U, reciprocal=reciprocal, rank=rank, world=world, reducer=reducer, save_path=save_path,
-               plain_params=plain_params)
+    ctx = dict(args=args, device=device, LF=LF, U=U, reciprocal=reciprocal, rank=rank, world=world, reducer=reducer, save_path=save_path)
     if args.tape is not False and device.type == "cuda":
         ctx["tape"] = TapedTrainer(args, LF, reciprocal, disp_net, optimizer, reducer, rank, explicit=args.tape is True)
 
@@ -440,6 +443,12 @@ def optimizer_state_name(optimizer):
     if hasattr(optimizer, "exp_avg"):
         return "Adam moments start"
     return "the SGD momentum buffer starts"
+
+
+def diff_lr_groups(disp_net, lr):
+    """The two parameter groups of --diff-lr (reference train.py:306-312): the network's pretrainable encoder at lr, its every other hot
+    parameter at 10 x lr."""
+    return [{"params": list(disp_net.get_1x_lr_params()), "lr": lr}, {"params": list(disp_net.get_10x_lr_params()), "lr": lr * 10}]
 
 
 def freeze_batchnorm(net):
@@ -649,9 +658,6 @@ def train(ctx, loader, disp_net, pose_exp_net, optimizer, epoch_size, n_iter):
         if reducer is not None:
             optimizer.step(grad_scale=reducer.finish())
         else:
-            if ctx["world"] > 1 and ctx["plain_params"] is not None:
-                from supervised_dispnet_amd.distributed import average_plain_grads
-                average_plain_grads(ctx["plain_params"])       # what DataParallel's reduce does for every optimizer (train.py:316)
             optimizer.step()
         lv = float(loss.item())
         losses.update(lv, args.batch_size)
