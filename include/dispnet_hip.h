@@ -494,6 +494,51 @@ int dn_edge_smooth_bwd(const float* disp, const float* img, const float* dloss, 
                        dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * monodepth2 self-supervision (csrc/dn_reproj.hip; reference layers.py:28-103,139-190).  Matrices are row-major 4x4 ([B][16]).
+ * ------------------------------------------------------------------------------------------------------------ */
+/* (axisangle, translation) -> M [F][B][16].  Element e of the vector of (batch b, frame f) is read at p[b*sb + f*sf + e*se] (views of one
+ * pose tensor: no contiguous copy).  mode 0: rot_from_axisangle (translation unused), 1: get_translation_matrix (axisangle unused),
+ * 2: transformation_from_parameters, M = T R, or R^T T(-t) for a frame whose bit of invert_mask is set.  angle = |v|,
+ * axis = v / (angle + 1e-7).  The backward writes daxisangle / dtranslation as contiguous [F][B][3] (either may be NULL). */
+int dn_pose_matrix_fwd(const float* axisangle, int64_t aa_sb, int64_t aa_sf, int64_t aa_se, const float* translation, int64_t t_sb,
+                       int64_t t_sf, int64_t t_se, int32_t B, int32_t F, int32_t mode, uint32_t invert_mask, float* M, dn_stream_t stream);
+int dn_pose_matrix_bwd(const float* axisangle, int64_t aa_sb, int64_t aa_sf, int64_t aa_se, const float* translation, int64_t t_sb,
+                       int64_t t_sf, int64_t t_se, int32_t B, int32_t F, int32_t mode, uint32_t invert_mask, const float* dM,
+                       float* daxisangle, float* dtranslation, dn_stream_t stream);
+/* BackprojectDepth: points [B][4][H*W], rows 0-2 = depth * inv_K[:3,:3] (x, y, 1), row 3 = 1 (the pixel grid is computed in the kernel). */
+int dn_backproject_fwd(const float* depth, const float* inv_K, int32_t B, int32_t H, int32_t W, float* points, dn_stream_t stream);
+int dn_backproject_bwd(const float* dpoints, const float* inv_K, int32_t B, int32_t H, int32_t W, float* ddepth, dn_stream_t stream);
+/* Project3D: grid [B][H][W][2] = ((c[:2] / (c[2] + eps)) / (W-1, H-1) - 0.5) * 2 with c = (K T)[:3,:] points; no clamp on c[2].
+ * Backward: dpoints [B][4][H*W], dT [B][16]; partial: [B * dn_reproj_blocks(H, W) * 12] scratch. */
+int32_t dn_reproj_blocks(int32_t H, int32_t W);
+int dn_project3d_fwd(const float* points, const float* K, const float* T, int32_t B, int32_t H, int32_t W, float eps, float* grid,
+                     dn_stream_t stream);
+int dn_project3d_bwd(const float* points, const float* K, const float* T, const float* dgrid, int32_t B, int32_t H, int32_t W, float eps,
+                     float* dpoints, float* partial, float* dT, dn_stream_t stream);
+/* One channel of the minimum-reprojection loss, term [B][H][W] = w * mean_c SSIM(pred, tgt) + (1 - w) * mean_c |tgt - pred|, in one launch.
+ * warp != 0: pred = ref sampled (bilinear, border padding, align_corners) where Project3D(BackprojectDepth(depth)) lands, computed per
+ * tile into LDS; depth = 1 / (d_lo + d_span * disp) (disp_mode 1) or disp itself (disp_mode 0).  warp == 0: pred = ref (the identity
+ * term of the automask; disp, K, inv_K, T unused). */
+int dn_reproj_term(const float* tgt, const float* ref, const float* disp, const float* K, const float* inv_K, const float* T, int32_t B,
+                   int32_t H, int32_t W, int32_t warp, int32_t align_corners, int32_t disp_mode, float d_lo, float d_span, float eps,
+                   float ssim_weight, float* term, dn_stream_t stream);
+/* m [n] = min over terms [C][n], sel [n] = the winning channel (a tie goes to the lowest), partial [dn_reproj_select_blocks(n)] scratch;
+ * loss (nullable) = mean(m), a fixed-order fp64 sum in a second launch. */
+int32_t dn_reproj_select_blocks(int64_t n);
+int dn_reproj_select(const float* terms, int32_t C, int64_t n, float* m, uint8_t* sel, float* partial, float* loss, dn_stream_t stream);
+/* Backward of one warped channel (two launches): the pixels with sel == channel carry dloss[0] / (B H W) (or dmap [B][H*W] when given).
+ * workspace: 9 * B * H * W floats.  ddisp [B][H*W] is overwritten or (accumulate != 0) added to; partial: [B * dn_reproj_blocks * 12]. */
+int dn_reproj_bwd(const float* tgt, const float* ref, const float* disp, const float* K, const float* inv_K, const float* T, int32_t B,
+                  int32_t H, int32_t W, int32_t align_corners, int32_t disp_mode, float d_lo, float d_span, float eps, float ssim_weight,
+                  const uint8_t* sel, int32_t channel, const float* dloss, const float* dmap, float* workspace, float* ddisp,
+                  int32_t accumulate, float* partial, dn_stream_t stream);
+/* partial [F][B][nblk][12] -> dT [F][B][16] (nullable) and, when the matrices came from dn_pose_matrix_fwd mode 2, the gradient of the
+ * pose parameters, written with the strides of the parameters themselves (daxisangle, dtranslation: nullable together). */
+int dn_reproj_pose_bwd(const float* partial, int32_t nblk, const float* K, int32_t B, int32_t F, float* dT, const float* axisangle,
+                       int64_t aa_sb, int64_t aa_sf, int64_t aa_se, const float* translation, int64_t t_sb, int64_t t_sf, int64_t t_se,
+                       uint32_t invert_mask, float* daxisangle, float* dtranslation, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DORN ordinal head and loss (models/Disp_vgg_BN_DORN.py:196-227, loss_functions.py:16-74, utils.py:106-175)
  * ------------------------------------------------------------------------------------------------------------ */
 /* OrdinalRegressionLayer: pre = logits, element (n, pixel, channel) at pre[n*stride_n + pixel*stride_pix + channel*stride_c]

@@ -52,7 +52,7 @@ class ConvDesc(C.Structure):
 
 
 _P = C.POINTER
-_i32, _i64, _f, _d, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p, C.c_size_t
+_i32, _u32, _i64, _f, _d, _vp, _sz = C.c_int32, C.c_uint32, C.c_int64, C.c_float, C.c_double, C.c_void_p, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/dispnet_hip.h declares (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -154,6 +154,19 @@ SIGNATURES = {
     "dn_edge_smooth_blocks": (_i32, [_i32, _i32, _i32]),
     "dn_edge_smooth_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_edge_smooth_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "dn_pose_matrix_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _u32, _vp, _vp]),
+    "dn_pose_matrix_bwd": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
+    "dn_backproject_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "dn_backproject_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "dn_reproj_blocks": (_i32, [_i32, _i32]),
+    "dn_project3d_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f, _vp, _vp]),
+    "dn_project3d_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp]),
+    "dn_reproj_term": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _f, _f, _vp, _vp]),
+    "dn_reproj_select_blocks": (_i32, [_i64]),
+    "dn_reproj_select": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "dn_reproj_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _f, _f, _f, _vp, _i32, _vp, _vp, _vp, _vp,
+                                _i32, _vp, _vp]),
+    "dn_reproj_pose_bwd": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _u32, _vp, _vp, _vp]),
     "dn_ordinal_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
     "dn_ordinal_bwd": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),
     "dn_ordinal_loss_blocks": (_i32, [_i32, _i64]),

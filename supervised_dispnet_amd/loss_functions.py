@@ -374,6 +374,161 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
                               1 if align_corners else 0, len(ref_imgs), n, has_mask, *args)
 
 
+# ------------------------------------------------------------------------------------------- monodepth2 minimum reprojection
+_MAX_REPROJ_FRAMES = 4
+
+
+def _pose_base(axisangle, translation):
+    """The dense [B, F, 6] tensor `axisangle` and `translation` are the two halves of (networks.PoseCNN attaches it to the views it
+    returns), or None: the loss then reads the pose through the base's strides and returns ONE gradient for it, without the slice
+    nodes -- framework kernels a launch tape cannot see -- in between."""
+    base = getattr(axisangle, "_dn_pose_base", None)
+    if base is None or getattr(translation, "_dn_pose_base", None) is not base:
+        return None
+    return base
+
+
+def _dense(t, what):
+    """`t` as a contiguous float32 tensor; the copy that may take is a framework kernel, which a launch tape would miss."""
+    require_cuda(t, "min_reprojection_loss: " + what)
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        from .engine import _not_on_tape
+        _not_on_tape("the contiguous float32 copy of %s" % what)
+        t = t.contiguous().float()
+    return t
+
+
+class _MinReproj(torch.autograd.Function):
+    """min_reprojection_loss as ONE autograd node: F (+ F identity) term launches, one select (+ finalize) forward; two launches per
+    source frame and one pose launch backward.  `pose`: None (T given as F matrices in `rest`) or the invert flags of the
+    (axisangle, translation) form, whose dense base then is rest[-1]."""
+
+    @staticmethod
+    def forward(ctx, tgt_img, disp, K, inv_K, cfg, pose, n_ref, *rest):
+        disp_mode, d_lo, d_span, automask, w, align, mean = cfg
+        refs, tail = rest[:n_ref], rest[n_ref:]
+        tgt, dc = _dense(tgt_img, "tgt_img"), _dense(disp, "disp")
+        refs = [_dense(r, "source frame") for r in refs]
+        Kc, Kic = _dense(K, "K"), _dense(inv_K, "inv_K")           # (torch.inverse hands out column-major matrices)
+        B, C3, H, W = tgt.shape
+        if C3 != 3 or tuple(dc.shape) != (B, 1, H, W) or tuple(Kc.shape) != (B, 4, 4) or tuple(Kic.shape) != (B, 4, 4):
+            raise ValueError("min_reprojection_loss: tgt_img [B,3,H,W], disp [B,1,H,W], K and inv_K [B,4,4] expected")
+        if any(r.shape != tgt.shape for r in refs):
+            raise ValueError("min_reprojection_loss: every source frame must have the target's shape")
+        dev = tgt.device
+        lib = _lib.load()
+        if pose is None:
+            base, mask = None, 0
+            Ts = [_dense(t, "T") for t in tail]
+            if any(tuple(t.shape) != (B, 4, 4) for t in Ts):
+                raise ValueError("min_reprojection_loss: every T must be [B,4,4]")
+        else:
+            base = tail[0]
+            require_cuda(base, "pose")
+            if base.dtype != torch.float32 or not base.is_contiguous() or base.numel() != B * n_ref * 6:
+                raise ValueError("min_reprojection_loss: the pose base must be a dense float32 [B, F, 6]")
+            mask = sum(1 << f for f, inv in enumerate(pose) if inv)
+            Tall = torch.empty((n_ref, B, 4, 4), dtype=torch.float32, device=dev)
+            _lib.call("dn_pose_matrix_fwd", base.data_ptr(), 6 * n_ref, 6, 1, base.data_ptr() + 12, 6 * n_ref, 6, 1, B, n_ref, 2, mask,
+                      Tall.data_ptr(), _stream())
+            Ts = [Tall[f] for f in range(n_ref)]
+        n = B * H * W
+        nch = (2 if automask else 1) * n_ref
+        terms = torch.empty((nch, B, H, W), dtype=torch.float32, device=dev)
+        common = (B, H, W)
+        tail_args = (align, disp_mode, d_lo, d_span, 1e-7, w)
+        for f, r in enumerate(refs):
+            if automask:
+                hbm_call("dn::reproj_term_kernel", 28 * n, "dn_reproj_term", tgt.data_ptr(), r.data_ptr(), None, None, None, None, *common, 0,
+                         *tail_args, terms[f].data_ptr(), _stream())
+            hbm_call("dn::reproj_term_kernel", 32 * n, "dn_reproj_term", tgt.data_ptr(), r.data_ptr(), dc.data_ptr(), Kc.data_ptr(), Kic.data_ptr(),
+                     Ts[f].data_ptr(), *common, 1, *tail_args, terms[(n_ref if automask else 0) + f].data_ptr(), _stream())
+        m = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        sel = torch.empty((B, 1, H, W), dtype=torch.uint8, device=dev)
+        partial = torch.empty(lib.dn_reproj_select_blocks(n), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev) if mean else None
+        hbm_call("dn::reproj_select_kernel", (4 * nch + 5) * n, "dn_reproj_select", terms.data_ptr(), nch, n, m.data_ptr(), sel.data_ptr(),
+                 partial.data_ptr(), loss.data_ptr() if mean else None, _stream())
+        ctx.saved = (tgt, refs, dc, Kc, Kic, Ts, sel, base)
+        ctx.cfg = (cfg, n_ref, mask, disp.shape)
+        ctx.mark_non_differentiable(sel)
+        return (loss if mean else m), sel
+
+    @staticmethod
+    def backward(ctx, dout, _dsel):
+        tgt, refs, dc, Kc, Kic, Ts, sel, base = ctx.saved
+        (disp_mode, d_lo, d_span, automask, w, align, mean), n_ref, mask, dshape = ctx.cfg
+        B, _, H, W = tgt.shape
+        dev = tgt.device
+        n = B * H * W
+        g = _dense(dout, "the upstream gradient")
+        nblk = _lib.load().dn_reproj_blocks(H, W)
+        ws = torch.empty(9 * n, dtype=torch.float32, device=dev)
+        partial = torch.empty((n_ref, B, nblk, 12), dtype=torch.float32, device=dev)
+        ddisp = torch.empty(dshape, dtype=torch.float32, device=dev)
+        for f, r in enumerate(refs):
+            hbm_call("dn::reproj_bwd_kernel", 120 * n, "dn_reproj_bwd", tgt.data_ptr(), r.data_ptr(), dc.data_ptr(), Kc.data_ptr(), Kic.data_ptr(),
+                     Ts[f].data_ptr(), B, H, W, align, disp_mode, d_lo, d_span, 1e-7, w, sel.data_ptr(), (n_ref if automask else 0) + f,
+                     g.data_ptr() if mean else None, None if mean else g.data_ptr(), ws.data_ptr(), ddisp.data_ptr(), 0 if f == 0 else 1,
+                     partial[f].data_ptr(), _stream())
+        if base is None:
+            dT = torch.empty((n_ref, B, 4, 4), dtype=torch.float32, device=dev)
+            _lib.call("dn_reproj_pose_bwd", partial.data_ptr(), nblk, Kc.data_ptr(), B, n_ref, dT.data_ptr(), None, 0, 0, 0, None, 0, 0, 0, 0,
+                      None, None, _stream())
+            tail = tuple(dT[f] for f in range(n_ref))
+        else:
+            dbase = torch.empty_like(base)
+            _lib.call("dn_reproj_pose_bwd", partial.data_ptr(), nblk, Kc.data_ptr(), B, n_ref, None, base.data_ptr(), 6 * n_ref, 6, 1,
+                      base.data_ptr() + 12, 6 * n_ref, 6, 1, mask, dbase.data_ptr(), dbase.data_ptr() + 12, _stream())
+            tail = (dbase,)
+        ctx.saved = None
+        return (None, ddisp, None, None, None, None, None) + (None,) * n_ref + tail
+
+
+def min_reprojection_loss(tgt_img, ref_imgs, disp, K, inv_K, T, min_depth=0.1, max_depth=100.0, automask=True, ssim_weight=0.85,
+                          align_corners=False, reduction="mean"):
+    """monodepth2's per-pixel minimum reprojection loss on the reference's layers (layers.py: disp_to_depth, BackprojectDepth,
+    Project3D, SSIM), fused: per source frame f
+        r_f = w * SSIM(pred_f, tgt).mean(1) + (1 - w) * |tgt - pred_f|.mean(1),   pred_f = grid_sample(ref_imgs[f], Project3D(
+              BackprojectDepth(depth, inv_K), K, T[f]), padding_mode="border", align_corners=align_corners)
+    and, with `automask`, the same term i_f of the unwarped source frame; m = min over [i_0 .. i_{F-1}, r_0 .. r_{F-1}] (a tie goes to
+    the lowest index, so identity terms win ties; monodepth2's random tie-breaker is not reproduced: the function is deterministic).
+    depth = disp_to_depth(disp, min_depth, max_depth)[1]; with min_depth=None `disp` IS the depth.  Returns m.mean(), or m [B,1,H,W]
+    for reduction="none"; the uint8 map of the winning channel rides on the result as `._dn_selection`.
+    `T`: F matrices [B,4,4], or (axisangle, translation, invert_flags) as networks.PoseCNN returns them ([B,F,1,3] each) with one flag
+    per frame (transformation_from_parameters's `invert`).  Gradients: disp and T (the pose); a pixel whose minimum is an identity
+    term carries none.  `align_corners` is F.grid_sample's flag, False being today's torch default (as in inverse_warp)."""
+    refs = list(ref_imgs)
+    n_ref = len(refs)
+    if not 1 <= n_ref <= _MAX_REPROJ_FRAMES:
+        raise ValueError("min_reprojection_loss takes 1 to %d source frames, got %d" % (_MAX_REPROJ_FRAMES, n_ref))
+    if reduction not in ("mean", "none"):
+        raise ValueError("reduction must be 'mean' or 'none'")
+    if min_depth is None:
+        depth_cfg = (0, 0.0, 0.0)
+    else:
+        depth_cfg = (1, 1.0 / max_depth, 1.0 / min_depth - 1.0 / max_depth)
+    cfg = depth_cfg + (bool(automask), float(ssim_weight), 1 if align_corners else 0, reduction == "mean")
+    pose, tail = None, None
+    if isinstance(T, (tuple, list)) and len(T) == 3 and isinstance(T[2], (tuple, list)) and not torch.is_tensor(T[2]):
+        axisangle, translation, flags = T
+        if len(flags) != n_ref or axisangle.shape[1] != n_ref or translation.shape[1] != n_ref:
+            raise ValueError("min_reprojection_loss: one pose and one invert flag per source frame expected")
+        base = _pose_base(axisangle, translation)
+        if base is not None:
+            pose, tail = tuple(bool(f) for f in flags), [base]
+        else:
+            from .layers import transformation_from_parameters
+            tail = [transformation_from_parameters(axisangle[:, f], translation[:, f], invert=bool(flags[f])) for f in range(n_ref)]
+    else:
+        tail = list(T)
+        if len(tail) != n_ref:
+            raise ValueError("min_reprojection_loss: %d source frames but %d transformations" % (n_ref, len(tail)))
+    out, sel = _MinReproj.apply(tgt_img, disp, K, inv_K, cfg, pose, n_ref, *(refs + tail))
+    out._dn_selection = sel
+    return out
+
+
 class _Explainability(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *masks):

@@ -1,7 +1,8 @@
 """Mirror of the reference's `networks` package for the hot path (reference networks/__init__.py:1-5): the monodepth2-style
-encoders / depth decoder on the HIP engine.  PoseDecoder / PoseCNN are dead code in the reference (imported, never
-instantiated) and are out of scope."""
+encoders / depth decoder and PoseCNN on the HIP engine.  PoseDecoder is dead code in the reference (imported, never instantiated) and
+is out of scope."""
 from .depth_decoder import DepthDecoder
+from .pose_cnn import PoseCNN
 from .resnet_encoder import ResnetEncoder
 from .vgg_encoder import vggEncoder
 
@@ -15,7 +16,6 @@ def _out_of_scope(name):
 
 
 PoseDecoder = _out_of_scope("PoseDecoder")
-PoseCNN = _out_of_scope("PoseCNN")
 
 
 def _no_replication(self):
@@ -24,5 +24,5 @@ def _no_replication(self):
     return f(self)
 
 
-for _c in (DepthDecoder, ResnetEncoder, vggEncoder):
+for _c in (DepthDecoder, ResnetEncoder, vggEncoder, PoseCNN):
     _c._replicate_for_data_parallel = _no_replication
