@@ -539,6 +539,43 @@ int dn_reproj_pose_bwd(const float* partial, int32_t nblk, const float* K, int32
                        uint32_t invert_mask, float* daxisangle, float* dtranslation, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * monodepth2's multi-scale objective (csrc/dn_mono2.hip): S <= 4 disparity maps, disp_s [B][H >> s][W >> s] (disp1..3 NULL beyond S),
+ * H and W divisible by 2^(S-1).  up_s = disp_s upsampled bilinearly (align_corners=False) to H x W, depth = 1 / (d_lo + d_span * up_s).
+ * The number of launches of every entry point is independent of S.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* The warped channel of one source frame at every scale in one launch: terms + s * scale_stride is the [B][H][W] term of scale s (the
+ * formula of dn_reproj_term with warp != 0); the upsampled disparity exists in registers only. */
+int dn_mono2_term(const float* tgt, const float* ref, const float* disp0, const float* disp1, const float* disp2, const float* disp3,
+                  const float* K, const float* inv_K, const float* T, int32_t B, int32_t H, int32_t W, int32_t S, int32_t align_corners,
+                  float d_lo, float d_span, float eps, float ssim_weight, float* terms, int64_t scale_stride, dn_stream_t stream);
+/* Per scale the minimum over [ident [n_ident][n] (shared by the scales; n_ident may be 0), warped [S][F][n]], a tie going to the lowest
+ * channel: sel [S][n], partial [S][dn_mono2_blocks(n)] = block sums of the minimum (times weights [S][n] when not NULL). */
+int32_t dn_mono2_blocks(int64_t n);
+int dn_mono2_select(const float* ident, int32_t n_ident, const float* warped, int32_t F, int32_t S, int64_t n, const float* weights,
+                    uint8_t* sel, float* partial, dn_stream_t stream);
+/* Three launches: mu [S][B] = per-sample mean of disp_s; the edge-aware smoothness of disp_s / (mu + 1e-7) under the 2^s x 2^s box
+ * average of tgt, per 8 x 32 tile of the coarse map (T = dn_mono2_tiles(H, W) tiles per sample): smooth_partial [S * B * T * 2] scratch,
+ * gbuf [sum_s B (H >> s)(W >> s)] = the gradient with respect to the normalised disparity and dot_partial [S * B * T] = the tiles' shares
+ * of sum_j g_j d_j, both kept for dn_mono2_disp_grad; parts [S][2] = (mean minimum, smoothness) and
+ * loss = (1 / S) sum_s (parts[s][0] + smoothness / 2^s * parts[s][1]) by fixed-order fp64 sums.  sel_partial: dn_mono2_select's. */
+int32_t dn_mono2_tiles(int32_t H, int32_t W);
+int dn_mono2_finish_fwd(const float* tgt, const float* disp0, const float* disp1, const float* disp2, const float* disp3, int32_t B, int32_t H,
+                        int32_t W, int32_t S, const float* sel_partial, float smoothness, float* mu, float* smooth_partial, float* gbuf,
+                        float* dot_partial, float* parts, float* loss, dn_stream_t stream);
+/* Backward of one warped channel at every scale (two launches): the pixels of scale s with sel == channel carry dloss[0] / (S B H W)
+ * (times weights).  workspace: S * 9 * B * H * W floats; ddfull [S][B][H*W], the gradient of the UPSAMPLED disparities, is overwritten
+ * or (accumulate != 0) added to; partial: [B][S * dn_reproj_blocks(H, W)][12], which dn_reproj_pose_bwd takes with nblk = S * blocks. */
+int dn_mono2_bwd(const float* tgt, const float* ref, const float* disp0, const float* disp1, const float* disp2, const float* disp3,
+                 const float* K, const float* inv_K, const float* T, int32_t B, int32_t H, int32_t W, int32_t S, int32_t align_corners,
+                 float d_lo, float d_span, float eps, float ssim_weight, const uint8_t* sel, int32_t channel, const float* dloss,
+                 const float* weights, float* workspace, float* ddfull, int32_t accumulate, float* partial, dn_stream_t stream);
+/* One launch: ddisp_s = upsampling^T ddfull[s] + dloss[0] * smoothness / (2^s S) * (g / (mu + 1e-7) - sum_j g_j d_j / (N (mu + 1e-7)^2)),
+ * a gather in a fixed order; mu, gbuf, dot_partial: dn_mono2_finish_fwd's. */
+int dn_mono2_disp_grad(int32_t B, int32_t H, int32_t W, int32_t S, const float* mu, const float* dloss, float smoothness, const float* ddfull,
+                       const float* gbuf, const float* dot_partial, float* ddisp0, float* ddisp1, float* ddisp2, float* ddisp3,
+                       dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DORN ordinal head and loss (models/Disp_vgg_BN_DORN.py:196-227, loss_functions.py:16-74, utils.py:106-175)
  * ------------------------------------------------------------------------------------------------------------ */
 /* OrdinalRegressionLayer: pre = logits, element (n, pixel, channel) at pre[n*stride_n + pixel*stride_pix + channel*stride_c]

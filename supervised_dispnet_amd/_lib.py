@@ -167,6 +167,13 @@ SIGNATURES = {
     "dn_reproj_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _f, _f, _f, _vp, _i32, _vp, _vp, _vp, _vp,
                                 _i32, _vp, _vp]),
     "dn_reproj_pose_bwd": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _u32, _vp, _vp, _vp]),
+    "dn_mono2_term": (C.c_int, [_vp] * 9 + [_i32] * 5 + [_f] * 4 + [_vp, _i64, _vp]),
+    "dn_mono2_blocks": (_i32, [_i64]),
+    "dn_mono2_select": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "dn_mono2_tiles": (_i32, [_i32, _i32]),
+    "dn_mono2_finish_fwd": (C.c_int, [_vp] * 5 + [_i32] * 4 + [_vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dn_mono2_bwd": (C.c_int, [_vp] * 9 + [_i32] * 5 + [_f] * 4 + [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "dn_mono2_disp_grad": (C.c_int, [_i32] * 4 + [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dn_ordinal_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
     "dn_ordinal_bwd": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),
     "dn_ordinal_loss_blocks": (_i32, [_i32, _i64]),

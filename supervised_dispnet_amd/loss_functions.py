@@ -529,6 +529,192 @@ def min_reprojection_loss(tgt_img, ref_imgs, disp, K, inv_K, T, min_depth=0.1, m
     return out
 
 
+# --------------------------------------------------------------------------------------- monodepth2's multi-scale objective
+_MAX_MONO2_SCALES = 4
+
+
+def _pose_view(v, base, what):
+    """(element offset into `base`, batch / frame / element strides) of a [B, F, 1, 3] view of the pose tensor `base`"""
+    if v.dim() != 4 or v.shape[2] != 1 or v.shape[3] != 3 or v.dtype != torch.float32:
+        raise ValueError("monodepth2_loss: %s must be a float32 [B, F, 1, 3] view of the pose, got %s" % (what, tuple(v.shape)))
+    off = (v.data_ptr() - base.data_ptr()) // 4
+    return (off, v.stride(0), v.stride(1), v.stride(3))
+
+
+class _Mono2(torch.autograd.Function):
+    """monodepth2_loss as ONE autograd node.  Forward: (the pose launch,) F identity launches, F warped launches over all scales, one
+    select, the means, the smoothness (which leaves its gradient behind), one finalize.  Backward: two launches per source frame over
+    all scales, the pose launch and the gather into the coarse maps.  No count depends on the number of scales.
+    rest = disps (n_scale), source frames (n_ref), then the F matrices or the pose base."""
+
+    @staticmethod
+    def forward(ctx, tgt_img, K, inv_K, cfg, pose, n_ref, n_scale, *rest):
+        d_lo, d_span, automask, w, align, smoothness, weights = cfg
+        S = n_scale
+        disps, refs, tail = rest[:S], rest[S:S + n_ref], rest[S + n_ref:]
+        tgt = _dense(tgt_img, "tgt_img")
+        dcs = [_dense(d, "the disparity of scale %d" % s) for s, d in enumerate(disps)]
+        refs = [_dense(r, "source frame") for r in refs]
+        Kc, Kic = _dense(K, "K"), _dense(inv_K, "inv_K")
+        B, _, H, W = tgt.shape
+        dev = tgt.device
+        lib = _lib.load()
+        st = _stream()
+        if pose is None:
+            base, mask, views = None, 0, None
+            Ts = [_dense(t, "T") for t in tail]
+            if any(tuple(t.shape) != (B, 4, 4) for t in Ts):
+                raise ValueError("monodepth2_loss: every T must be [B,4,4]")
+        else:
+            base = tail[0]
+            flags, va, vt = pose
+            views = va + vt
+            mask = sum(1 << f for f, inv in enumerate(flags) if inv)
+            Tall = torch.empty((n_ref, B, 4, 4), dtype=torch.float32, device=dev)
+            _lib.call("dn_pose_matrix_fwd", base.data_ptr() + 4 * va[0], va[1], va[2], va[3], base.data_ptr() + 4 * vt[0], vt[1], vt[2], vt[3],
+                      B, n_ref, 2, mask, Tall.data_ptr(), st)
+            Ts = [Tall[f] for f in range(n_ref)]
+        n = B * H * W
+        dptr = [d.data_ptr() for d in dcs] + [None] * (_MAX_MONO2_SCALES - S)
+        tail_args = (align, d_lo, d_span, 1e-7, w)
+        ident = torch.empty((n_ref, B, H, W), dtype=torch.float32, device=dev) if automask else None
+        warped = torch.empty((S, n_ref, B, H, W), dtype=torch.float32, device=dev)
+        for f, r in enumerate(refs):
+            if automask:         # the identity terms do not depend on the scale: once per frame, the launch of min_reprojection_loss
+                hbm_call("dn::reproj_term_kernel", 28 * n, "dn_reproj_term", tgt.data_ptr(), r.data_ptr(), None, None, None, None, B, H, W, 0,
+                         align, 1, d_lo, d_span, 1e-7, w, ident[f].data_ptr(), st)
+            hbm_call("dn::mono2_term_kernel", 32 * n * S, "dn_mono2_term", tgt.data_ptr(), r.data_ptr(), *dptr, Kc.data_ptr(), Kic.data_ptr(),
+                     Ts[f].data_ptr(), B, H, W, S, *tail_args, warped[0, f].data_ptr(), n_ref * n, st)
+        sel = torch.empty((S, B, 1, H, W), dtype=torch.uint8, device=dev)
+        partial = torch.empty(S * lib.dn_mono2_blocks(n), dtype=torch.float32, device=dev)
+        nch = (2 if automask else 1) * n_ref
+        hbm_call("dn::mono2_select_kernel", (4 * nch + 1) * n * S, "dn_mono2_select", ident.data_ptr() if automask else None,
+                 n_ref if automask else 0, warped.data_ptr(), n_ref, S, n, None if weights is None else weights.data_ptr(), sel.data_ptr(),
+                 partial.data_ptr(), st)
+        tiles = lib.dn_mono2_tiles(H, W)
+        mu = torch.empty(S * B, dtype=torch.float32, device=dev)
+        smp = torch.empty(S * B * tiles * 2, dtype=torch.float32, device=dev)
+        gbuf = torch.empty(sum(d.numel() for d in dcs), dtype=torch.float32, device=dev)
+        dotp = torch.empty(S * B * tiles, dtype=torch.float32, device=dev)
+        parts = torch.empty((S, 2), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        hbm_call("dn::mono2_smooth_kernel", 16 * n, "dn_mono2_finish_fwd", tgt.data_ptr(), *dptr, B, H, W, S, partial.data_ptr(), smoothness,
+                 mu.data_ptr(), smp.data_ptr(), gbuf.data_ptr(), dotp.data_ptr(), parts.data_ptr(), loss.data_ptr(), st)
+        ctx.saved = (tgt, refs, dcs, Kc, Kic, Ts, sel, base, (mu, gbuf, dotp), weights)
+        ctx.cfg = (cfg, n_ref, mask, views, [d.shape for d in disps])
+        ctx.mark_non_differentiable(parts, sel)
+        return loss, parts, sel
+
+    @staticmethod
+    def backward(ctx, dout, _dparts, _dsel):
+        tgt, refs, dcs, Kc, Kic, Ts, sel, base, (mu, gbuf, dotp), weights = ctx.saved
+        (d_lo, d_span, automask, w, align, smoothness, _), n_ref, mask, views, shapes = ctx.cfg
+        S = len(dcs)
+        B, _, H, W = tgt.shape
+        dev = tgt.device
+        n = B * H * W
+        st = _stream()
+        g = _dense(dout, "the upstream gradient")
+        nblk = _lib.load().dn_reproj_blocks(H, W)
+        dptr = [d.data_ptr() for d in dcs] + [None] * (_MAX_MONO2_SCALES - S)
+        ws = torch.empty(S * 9 * n, dtype=torch.float32, device=dev)
+        ddfull = torch.empty(S * n, dtype=torch.float32, device=dev)
+        partial = torch.empty((n_ref, B, S * nblk, 12), dtype=torch.float32, device=dev)
+        for f, r in enumerate(refs):
+            hbm_call("dn::mono2_bwd_kernel", 120 * n * S, "dn_mono2_bwd", tgt.data_ptr(), r.data_ptr(), *dptr, Kc.data_ptr(), Kic.data_ptr(),
+                     Ts[f].data_ptr(), B, H, W, S, align, d_lo, d_span, 1e-7, w, sel.data_ptr(), (n_ref if automask else 0) + f, g.data_ptr(),
+                     None if weights is None else weights.data_ptr(), ws.data_ptr(), ddfull.data_ptr(), 0 if f == 0 else 1,
+                     partial[f].data_ptr(), st)
+        if base is None:
+            dT = torch.empty((n_ref, B, 4, 4), dtype=torch.float32, device=dev)
+            _lib.call("dn_reproj_pose_bwd", partial.data_ptr(), S * nblk, Kc.data_ptr(), B, n_ref, dT.data_ptr(), None, 0, 0, 0, None, 0, 0, 0, 0,
+                      None, None, st)
+            tail = tuple(dT[f] for f in range(n_ref))
+        else:
+            dbase = torch.empty_like(base)
+            _lib.call("dn_reproj_pose_bwd", partial.data_ptr(), S * nblk, Kc.data_ptr(), B, n_ref, None, base.data_ptr() + 4 * views[0], views[1],
+                      views[2], views[3], base.data_ptr() + 4 * views[4], views[5], views[6], views[7], mask, dbase.data_ptr() + 4 * views[0],
+                      dbase.data_ptr() + 4 * views[4], st)
+            tail = (dbase,)
+        outs = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
+        optr = [o.data_ptr() for o in outs] + [None] * (_MAX_MONO2_SCALES - S)
+        hbm_call("dn::mono2_disp_grad_kernel", 10 * n, "dn_mono2_disp_grad", B, H, W, S, mu.data_ptr(), g.data_ptr(), smoothness, ddfull.data_ptr(),
+                 gbuf.data_ptr(), dotp.data_ptr(), *optr, st)
+        ctx.saved = None
+        return (None,) * 7 + tuple(outs) + (None,) * n_ref + tail
+
+
+def monodepth2_loss(tgt_img, ref_imgs, disps, K, inv_K, T, min_depth=0.1, max_depth=100.0, scaled_disp=False, automask=True,
+                    ssim_weight=0.85, smoothness=1e-3, align_corners=False, _pixel_weights=None):
+    """monodepth2's training objective over the S = len(disps) scales of the decoder, disps[s] [B,1,H>>s,W>>s] (S from 1 to 4, H and W
+    divisible by 2^(S-1)), fused.  Per scale s:
+        up_s    = F.interpolate(disps[s], (H, W), mode="bilinear", align_corners=False)                    (up_0 = disps[0])
+        depth_s = 1 / up_s  (scaled_disp=True: networks.DepthDecoder already emits 0.01 + 9.99 sigma)  or  disp_to_depth(up_s, min_depth,
+                  max_depth)[1]
+        m_s     = the per-pixel minimum over [i_0 .. i_{F-1}, r_{s,0} .. r_{s,F-1}] of min_reprojection_loss (a tie goes to the lowest
+                  index; the identity terms i_f of `automask` do not depend on s and are computed once)
+        norm_s  = disps[s] / (disps[s].mean((2, 3), keepdim=True) + 1e-7)
+        loss    = (1 / S) * sum_s [ m_s.mean() + smoothness / 2^s * get_smooth_loss(norm_s, colour_s) ]
+    with colour_s the 2^s x 2^s box average of tgt_img (F.interpolate(mode="area")).  A direction in which a map has no neighbour pair
+    (a map one pixel high or wide) contributes 0 to its smoothness, where the mean of an empty tensor would be NaN.
+    tgt_img, ref_imgs, K, inv_K, T (F matrices, or (axisangle, translation, invert_flags)) and align_corners (the sampler's flag; the
+    upsampling is always align_corners=False) are min_reprojection_loss's.  Returns the scalar; `._dn_parts` [S,2] holds the
+    reprojection mean and the unweighted smoothness per scale (device tensor: logging without a sync), `._dn_selection` the S uint8
+    maps of the winning channel.  Gradients: every disps[s] and T (the pose).  Deterministic: every sum has a fixed order.
+    `_pixel_weights` ([S,B,1,H,W], the fp64 audit's handle): m_s.mean() becomes (m_s * _pixel_weights[s]).mean()."""
+    refs, disps = list(ref_imgs), list(disps)
+    n_ref, S = len(refs), len(disps)
+    if not 1 <= n_ref <= _MAX_REPROJ_FRAMES:
+        raise ValueError("monodepth2_loss takes 1 to %d source frames, got %d" % (_MAX_REPROJ_FRAMES, n_ref))
+    if not 1 <= S <= _MAX_MONO2_SCALES:
+        raise ValueError("monodepth2_loss takes 1 to %d disparity maps, got %d" % (_MAX_MONO2_SCALES, S))
+    if tgt_img.dim() != 4 or tgt_img.shape[1] != 3:
+        raise ValueError("monodepth2_loss: tgt_img [B,3,H,W] expected")
+    B, _, H, W = tgt_img.shape
+    if H < 2 or W < 2 or H % (1 << (S - 1)) or W % (1 << (S - 1)):
+        raise ValueError("monodepth2_loss: %d x %d is not divisible by 2^%d" % (H, W, S - 1))
+    for s, d in enumerate(disps):
+        if tuple(d.shape) != (B, 1, H >> s, W >> s):
+            raise ValueError("monodepth2_loss: disps[%d] must be %s, got %s" % (s, (B, 1, H >> s, W >> s), tuple(d.shape)))
+    if any(r.shape != tgt_img.shape for r in refs):
+        raise ValueError("monodepth2_loss: every source frame must have the target's shape")
+    if tuple(K.shape) != (B, 4, 4) or tuple(inv_K.shape) != (B, 4, 4):
+        raise ValueError("monodepth2_loss: K and inv_K [B,4,4] expected")
+    if scaled_disp:
+        d_lo, d_span = 0.0, 1.0
+    else:
+        d_lo, d_span = 1.0 / max_depth, 1.0 / min_depth - 1.0 / max_depth
+    weights = None
+    if _pixel_weights is not None:
+        weights = _dense(_pixel_weights.detach(), "_pixel_weights")
+        if tuple(weights.shape) != (S, B, 1, H, W):
+            raise ValueError("monodepth2_loss: _pixel_weights must be [S,B,1,H,W]")
+    cfg = (d_lo, d_span, bool(automask), float(ssim_weight), 1 if align_corners else 0, float(smoothness), weights)
+    pose = None
+    if isinstance(T, (tuple, list)) and len(T) == 3 and isinstance(T[2], (tuple, list)) and not torch.is_tensor(T[2]):
+        axisangle, translation, flags = T
+        if len(flags) != n_ref or axisangle.shape[1] != n_ref or translation.shape[1] != n_ref or axisangle.shape[0] != B:
+            raise ValueError("monodepth2_loss: one pose and one invert flag per source frame expected")
+        base = _pose_base(axisangle, translation)
+        if base is not None:
+            require_cuda(base, "pose")
+            if base.dtype != torch.float32 or not base.is_contiguous() or base.numel() != B * n_ref * 6:
+                raise ValueError("monodepth2_loss: the pose base must be a dense float32 tensor of B * F * 6 elements")
+            pose = (tuple(bool(f) for f in flags), _pose_view(axisangle, base, "axisangle"), _pose_view(translation, base, "translation"))
+            tail = [base]
+        else:
+            from .layers import transformation_from_parameters
+            tail = [transformation_from_parameters(axisangle[:, f], translation[:, f], invert=bool(flags[f])) for f in range(n_ref)]
+    else:
+        tail = list(T)
+        if len(tail) != n_ref:
+            raise ValueError("monodepth2_loss: %d source frames but %d transformations" % (n_ref, len(tail)))
+    out, parts, sel = _Mono2.apply(tgt_img, K, inv_K, cfg, pose, n_ref, S, *(disps + refs + tail))
+    out._dn_parts = parts
+    out._dn_selection = [sel[s] for s in range(S)]
+    return out
+
+
 class _Explainability(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *masks):

@@ -107,6 +107,14 @@ def build_parser():
                    help="fine-tune with frozen BatchNorm statistics: every BatchNorm of the depth network runs in eval mode inside the "
                         "training step (running statistics normalise and do not move; gamma, beta and the conv biases in front still "
                         "train).  Meant for --pretrained-disp; works with Adam and --sgd, with and without the launch tape")
+    p.add_argument("--min-reprojection", action="store_true",
+                   help="with --unsupervised --monodepth2: train with monodepth2's own objective (loss_functions.monodepth2_loss: per-pixel "
+                        "minimum reprojection with automasking over the decoder's four scales + edge-aware smoothness weighted by -s) and "
+                        "networks.PoseCNN on the frame pairs, both networks in the optimizer; --pretrained-exppose then names a monodepth2 "
+                        "pose.pth, and the pose checkpoint takes the place of the PoseExpNet one")
+    p.add_argument("--min-depth", type=float, default=0.1, help="--min-reprojection: monodepth2's min_depth")
+    p.add_argument("--max-depth", type=float, default=100.0, help="--min-reprojection: monodepth2's max_depth")
+    p.add_argument("--no-automask", action="store_true", help="--min-reprojection: without the identity-reprojection terms")
     p.add_argument("--save-root", default="checkpoints", help="directory under which the run folder is created")
     p.add_argument("--legacy-align-corners", action="store_true",
                    help="photometric warp with F.grid_sample(align_corners=True): the sampling the reference's pinned torch 1.0.1 did at "
@@ -212,6 +220,8 @@ class Meter(object):
 
 def check_dataset_args(args):
     """Settings the NYU Depth v2 loader cannot serve, refused before anything touches the GPU (one line each)."""
+    if args.min_reprojection and not (args.unsupervised and args.monodepth2):
+        raise SystemExit("--min-reprojection is monodepth2's objective: it needs --unsupervised --monodepth2")
     if args.scale_crop and args.synthetic > 0:
         raise SystemExit("--scale-crop augments decoded frames (scene folders or --shards); --synthetic samples are generated normalised")
     if args.scale_crop and args.dataset == "nyu":
@@ -335,7 +345,15 @@ def main(argv=None):
     disp_net = create_disp_net(args, models, networks, device, U)
     output_exp = args.mask_loss_weight > 0
     pose_exp_net = models.PoseExpNet(nb_ref_imgs=args.sequence_length - 1, output_exp=output_exp).to(device)
-    if args.pretrained_exp_pose:
+    pose_cnn = None
+    if args.min_reprojection:
+        # monodepth2's pose network on frame pairs; PoseExpNet stays what validation without ground truth runs, untrained
+        pose_cnn = networks.PoseCNN(num_input_frames=2).to(device)
+        if args.pretrained_exp_pose:
+            state = torch.load(args.pretrained_exp_pose, map_location=device)
+            pose_cnn.load_state_dict(state.get("state_dict", state))          # a monodepth2 pose.pth is the bare state_dict
+        pose_exp_net.init_weights()
+    elif args.pretrained_exp_pose:
         pose_exp_net.load_state_dict(torch.load(args.pretrained_exp_pose, map_location=device)["state_dict"], strict=False)
     else:
         pose_exp_net.init_weights()
@@ -351,6 +369,8 @@ def main(argv=None):
     hot =list(disp_net._hot_parameters()) if hasattr(disp_net, "_hot_parameters") else [p for p in disp_net.parameters() if p.requires_grad]
     if args.train_pose:
         hot += [p for p in pose_exp_net.parameters() if p.requires_grad]
+    if pose_cnn is not None:
+        hot += list(pose_cnn._hot_parameters())
     reducer = None
     order = disp_net._grad_production_order() if hasattr(disp_net, "_grad_production_order") else None
     if args.diff_lr:
@@ -389,7 +409,8 @@ def main(argv=None):
         with open(os.path.join(save_path, args.log_full), "w") as f:
             csv.writer(f, delimiter="\t").writerow(["train_loss", "photo_loss", "explainability_loss", "smooth_loss"])
 
-    ctx = dict(args=args, device=device, LF=LF, U=U, reciprocal=reciprocal, rank=rank, world=world, reducer=reducer, save_path=save_path)
+    ctx = dict(args=args, device=device, LF=LF, U=U, reciprocal=reciprocal, rank=rank, world=world, reducer=reducer, save_path=save_path,
+               pose_cnn=pose_cnn)
     if args.tape is not False and device.type == "cuda":
         ctx["tape"] = TapedTrainer(args, LF, reciprocal, disp_net, optimizer, reducer, rank, explicit=args.tape is True)
 
@@ -419,7 +440,8 @@ def main(argv=None):
             best_error = min(best_error, decisive)
             save_checkpoint(save_path,
                             {"epoch": epoch + 1, "state_dict": disp_net.state_dict(), "optimizer": optimizer.state_dict()},
-                            {"epoch": epoch + 1, "state_dict": pose_exp_net.state_dict()}, is_best, epoch, record=args.record)
+                            {"epoch": epoch + 1, "state_dict": (pose_cnn if pose_cnn is not None else pose_exp_net).state_dict()},
+                            is_best, epoch, record=args.record)
             with open(os.path.join(save_path, args.log_summary), "a") as f:
                 csv.writer(f, delimiter="\t").writerow([train_loss, decisive])
     if ctx.get("tape") is not None:
@@ -429,9 +451,19 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def _to_device_batch(batch, device, unsupervised):
+def _homogeneous(m):
+    """[B,3,3] -> [B,4,4] = [[m, 0], [0, 1]] (on the host: monodepth2's K and inv_K)"""
+    m = torch.as_tensor(m).float()
+    out = torch.eye(4).repeat(m.shape[0], 1, 1)
+    out[:, :3, :3] = m
+    return out
+
+
+def _to_device_batch(batch, device, unsupervised, homogeneous=False):
     if unsupervised:
         tgt, refs, intr, intr_inv, gt = batch
+        if homogeneous:
+            intr, intr_inv = _homogeneous(intr), _homogeneous(intr_inv)
         return (tgt.to(device, non_blocking=True), [r.to(device, non_blocking=True) for r in refs],
                 torch.as_tensor(intr).float().to(device), torch.as_tensor(intr_inv).float().to(device), gt.to(device, non_blocking=True))
     tgt, gt = batch
@@ -591,12 +623,31 @@ class TapedTrainer(object):
             return None
 
 
+def min_reprojection_objective(args, LF, disp_net, pose_cnn, tgt_img, ref_imgs, K, inv_K):
+    """monodepth2's training objective for one batch.  The pose network runs ONCE on the F * B stacked pairs in temporal order --
+    [ref, tgt] for a frame before the target (its pose is inverted), [tgt, ref] for one after it; it has no batch statistics, so this
+    equals F calls -- and the loss reads the frame-major result [F, B, 6] through its strides: no slice, no copy."""
+    B, F = tgt_img.shape[0], len(ref_imgs)
+    earlier = [f < F // 2 for f in range(F)]
+    pairs = torch.cat([torch.cat([r, tgt_img] if e else [tgt_img, r], 1) for r, e in zip(ref_imgs, earlier)], 0)
+    axisangle, _translation = pose_cnn(pairs)
+    base = axisangle._dn_pose_base                                   # dense [F * B, 6, 1, 1]
+    v = base.view(F, B, 1, 6).permute(1, 0, 2, 3)                    # [B, F, 1, 6]: batch stride 6, frame stride 6 B
+    aa, tr = v[..., :3], v[..., 3:]
+    aa._dn_pose_base = tr._dn_pose_base = base
+    return LF.monodepth2_loss(tgt_img, ref_imgs, disp_net(tgt_img), K, inv_K, (aa, tr, earlier), min_depth=args.min_depth,
+                              max_depth=args.max_depth, scaled_disp=True, automask=not args.no_automask,
+                              smoothness=args.smooth_loss_weight, align_corners=args.legacy_align_corners)
+
+
 def train(ctx, loader, disp_net, pose_exp_net, optimizer, epoch_size, n_iter):
     args, device, LF, U, reciprocal = ctx["args"], ctx["device"], ctx["LF"], ctx["U"], ctx["reciprocal"]
     rank, reducer = ctx["rank"], ctx["reducer"]
     w1, w2, w3 = args.photo_loss_weight, args.mask_loss_weight, args.smooth_loss_weight
     disp_net.train()
     pose_exp_net.train()
+    if ctx.get("pose_cnn") is not None:
+        ctx["pose_cnn"].train()
     if args.diff_lr:          # freeze BN (train.py:406-411)
         for m in disp_net.modules():
             if m.__class__.__name__.find("BatchNorm") != -1:
@@ -608,7 +659,30 @@ def train(ctx, loader, disp_net, pose_exp_net, optimizer, epoch_size, n_iter):
     tape = ctx.get("tape")
     for i, batch in enumerate(loader):
         data_time.update(time.time() - end)
-        tgt_img, ref_imgs, intrinsics, intrinsics_inv, gt_depth = _to_device_batch(batch, device, args.unsupervised)
+        tgt_img, ref_imgs, intrinsics, intrinsics_inv, gt_depth = _to_device_batch(batch, device, args.unsupervised, args.min_reprojection)
+        if args.min_reprojection:
+            loss = min_reprojection_objective(args, LF, disp_net, ctx["pose_cnn"], tgt_img, ref_imgs, intrinsics, intrinsics_inv)
+            optimizer.zero_grad()
+            loss.backward()
+            if reducer is not None:
+                optimizer.step(grad_scale=reducer.finish())
+            else:
+                optimizer.step()
+            parts = loss._dn_parts.mean(0).tolist()                  # (reprojection, unweighted smoothness) averaged over the scales
+            lv = float(loss.item())
+            losses.update(lv, args.batch_size)
+            batch_time.update(time.time() - end)
+            end = time.time()
+            if rank == 0:
+                with open(os.path.join(ctx["save_path"], args.log_full), "a") as f:
+                    csv.writer(f, delimiter="\t").writerow([lv, parts[0], 0, parts[1]])
+                if i % args.print_freq == 0:
+                    print("Train: [{}/{}] Time {:.3f} ({:.3f}) Data {:.3f} Loss {:.4f} ({:.4f})".format(
+                        i, min(len(loader), epoch_size), batch_time.val[0], batch_time.avg[0], data_time.avg[0], lv, losses.avg[0]))
+            if i >= epoch_size - 1:
+                break
+            n_iter += 1
+            continue
         if tape is not None and tape.usable(tgt_img, gt_depth):
             lv = tape.step(tgt_img, gt_depth)
             if lv is not None:
