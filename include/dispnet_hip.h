@@ -48,7 +48,7 @@ enum dn_status {
 void dn_reload_knobs(void);          /* re-read the DN_* tuning / test switches (they are read once, at first use) */
 int dn_version(void);                 /* ABI version, bumped on any signature/struct change */
 const char* dn_last_error(void);      /* thread-local, valid until the next failing call on this thread */
-const char* dn_last_kernel(void);     /* thread-local: name (as rocprofv3 prints it) of the main kernel the last conv-family call launched */
+const char* dn_last_kernel(void);     /* thread-local: name (as rocprofv3 prints it) of the main kernel the last conv-family (or dn_colour_jitter_*) call launched */
 int dn_device_arch_ok(void);          /* 1 if the current HIP device is gfx950, 0 otherwise, <0 on error */
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -750,6 +750,36 @@ int dn_scale_crop_u8(const uint8_t* frames, const uint8_t* flip, int32_t N, int3
                      float* out, dn_stream_t stream);
 int dn_scale_crop_depth(const float* depth, const uint8_t* flip, int32_t B, int32_t H, int32_t W, const float* minmax_depth,
                         const int32_t* table, const int32_t* scaled_hw_host, int32_t max_taps, float* out, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * monodepth2's colour jitter of the shard loader, fused with the flip and the normalisation above.  Equality with
+ * the host chain (data.colour_jitter_u8 -- Pillow itself --, then data.Transform.apply) is the contract: no tolerance.
+ * frames = uint8 [N][B][H][W][3] (N images per sample: target, references); params = int32 [B][DN_COLOUR_PARAMS] on the device, one row
+ * per sample shared by its N frames: {jittered (0 / 1), order, fp32 bits of the brightness, contrast and saturation factors, hue shift in
+ * 0..255, 0, 0}; order = the four operations in the sequence they are applied, 2 bits each, the first in the low bits: 0 brightness,
+ * 1 contrast, 2 saturation, 3 hue (each exactly once; an order that names contrast twice applies it twice with the first one's mean).
+ * Per operation, on the frame as it is at that point of the chain (every blend in fp32 WITHOUT a fused multiply-add, clipped to
+ * [0, 255] and truncated: blend(a, x, f) = fp32(a) + f * (fp32(x) - fp32(a))):
+ *   brightness  blend(0, x, b);   saturation  blend(L, x, s), L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16;
+ *   contrast    blend(m, x, c), m = int(sum(L) / (H * W) + 0.5) over the whole frame (integer sum, one fp64 division);
+ *   hue         Pillow's rgb2hsv_row (V = max; grey -> H = S = 0; else fp32 quotients, the hue sextant in double rounded to fp32,
+ *               fmod(h / 6 + 1, 1) in double, H and S = the double products with 255.0 truncated), H = (H + shift) mod 256, Pillow's
+ *               hsv2rgb (double, round half away).  Taken also for shift 0: the round trip is lossy.
+ * dn_colour_jitter_sums writes sum_ws = uint64 [N * B][DN_IMAGE_CHUNKS], the partial sums of L of every jittered frame after the
+ * operations that precede contrast in its order (rows of unjittered samples are left untouched and never read).
+ * dn_colour_jitter_normalize_flip: out = fp32 [N][B][3][H][W] = dn_u8_normalize_flip (same flip rule, same arithmetic) of the jittered
+ * bytes; plain (or NULL) = the same of the bytes as they came, from the same read.  An unjittered sample gives out == plain.
+ * dn_colour_jitter_u8: out = uint8 [N][B][H][W][3], the jittered bytes (a copy for an unjittered sample), no flip; out != frames.
+ * Any H, W; N * B <= 65535.  mean_host / std_host: 3 floats each on the host.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DN_COLOUR_PARAMS 8
+int dn_colour_jitter_sums(const uint8_t* frames, const int32_t* params, int32_t N, int32_t B, int32_t H, int32_t W, uint64_t* sum_ws,
+                          dn_stream_t stream);
+int dn_colour_jitter_normalize_flip(const uint8_t* frames, const uint8_t* flip, const int32_t* params, const uint64_t* sum_ws, int32_t N,
+                                    int32_t B, int32_t H, int32_t W, const float* mean_host, const float* std_host, float* out, float* plain,
+                                    dn_stream_t stream);
+int dn_colour_jitter_u8(const uint8_t* frames, const int32_t* params, const uint64_t* sum_ws, int32_t N, int32_t B, int32_t H, int32_t W,
+                        uint8_t* out, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * NYU Depth v2 input chain (reference datasets/nyu_depth_v2.py:76-110).  Training: raw = the stored samples [B,5,H0,W0] fp32 (RGB 0..255,

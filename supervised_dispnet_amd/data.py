@@ -69,24 +69,74 @@ def imresize_crop(a, sh, sw, oy, ox):
     return np.array(im)[oy:oy + H, ox:ox + W]
 
 
-class Transform(object):
-    """flip (train only) -> [scale and crop (train only)] -> CHW float /255 -> normalise, applied coherently to images, depth and
-    intrinsics.  `scale_crop` is the reference's RandomScaleCrop (custom_transforms.py:73-113) in its Compose position, drawn from the
-    global numpy.random as the reference's workers do; it is the host statement of what dn_scale_crop_u8 / _depth compute."""
+def draw_colour_jitter(rng, brightness=0.2, contrast=0.2, saturation=0.2, hue=0.1, prob=0.5):
+    """monodepth2's colour jitter draw for one sample (all its frames share it) from `rng` (numpy.random or a RandomState): always the
+    same seven calls in the same order, whether or not the sample is jittered, so a sample's draw never moves the next one's.
+    -> None, or (order, b, c, s, shift): the order of the four operations (0 brightness, 1 contrast, 2 saturation, 3 hue), the three
+    factors and the hue shift in Pillow's 8-bit hue units, np.uint8(h * 255) as torchvision forms it (truncated, then mod 256)."""
+    u = rng.random_sample()
+    order = rng.permutation(4)
+    b = rng.uniform(1 - brightness, 1 + brightness)
+    c = rng.uniform(1 - contrast, 1 + contrast)
+    s = rng.uniform(1 - saturation, 1 + saturation)
+    h = rng.uniform(-hue, hue)
+    if not u > prob:
+        return None
+    return tuple(int(o) for o in order), float(b), float(c), float(s), int(h * 255) % 256
 
-    def __init__(self, mean, std, flip, scale_crop=False):
+
+def colour_jitter_u8(frame, params):
+    """The jitter of one uint8 [H, W, 3] frame (or a float array holding such integers) with Pillow itself, operation by operation as
+    torchvision's ColorJitter applies them: ImageEnhance.Brightness / Contrast / Color, and the HSV round trip with the hue channel
+    shifted mod 256 (taken also when the shift is 0).  The host statement of dn_colour_jitter_*; the JPEG loader runs it."""
+    a = np.ascontiguousarray(np.asarray(frame).astype(np.uint8))
+    if params is None:
+        return a
+    from PIL import Image, ImageEnhance
+    order, b, c, s, shift = params
+    im = Image.fromarray(a)
+    for op in order:
+        if op == 0:
+            im = ImageEnhance.Brightness(im).enhance(b)
+        elif op == 1:
+            im = ImageEnhance.Contrast(im).enhance(c)
+        elif op == 2:
+            im = ImageEnhance.Color(im).enhance(s)
+        else:
+            h, sat, v = im.convert("HSV").split()
+            nh = ((np.asarray(h, dtype=np.int32) + int(shift)) % 256).astype(np.uint8)
+            im = Image.merge("HSV", (Image.fromarray(nh), sat, v)).convert("RGB")
+    return np.asarray(im, dtype=np.uint8)
+
+
+class Transform(object):
+    """[colour jitter (train only)] -> flip (train only) -> [scale and crop (train only)] -> CHW float /255 -> normalise, applied
+    coherently to images, depth and intrinsics.  `scale_crop` is the reference's RandomScaleCrop (custom_transforms.py:73-113) in its
+    Compose position, drawn from the global numpy.random as the reference's workers do; it is the host statement of what
+    dn_scale_crop_u8 / _depth compute.  `color_aug` is monodepth2's colour jitter (draw_colour_jitter / colour_jitter_u8, DESIGN.md
+    section 19) on the decoded frames, one draw per sample from the global numpy.random in front of the scale-crop draws; with
+    `keep_plain` the returned list holds the n augmented tensors followed by the n plain ones (same flip, same crop)."""
+
+    def __init__(self, mean, std, flip, scale_crop=False, color_aug=False, keep_plain=False):
         self.mean = torch.tensor(mean, dtype=torch.float32).view(3, 1, 1)
         self.std = torch.tensor(std, dtype=torch.float32).view(3, 1, 1)
         self.flip = flip
         self.scale_crop = scale_crop
+        self.color_aug = color_aug
+        self.keep_plain = bool(color_aug and keep_plain)
 
     def __call__(self, images, gt_depth, intrinsics):
         flip = bool(self.flip and random.random() < 0.5)
+        jitter = draw_colour_jitter(np.random) if self.color_aug else None
         crop = draw_scale_crop(np.random, *images[0].shape[:2]) if self.scale_crop else None
-        return self.apply(images, gt_depth, intrinsics, flip, crop)
+        if not self.color_aug:
+            return self.apply(images, gt_depth, intrinsics, flip, crop)
+        frames = [colour_jitter_u8(im, jitter).astype(np.float32) for im in images]
+        # one pass for both halves: every frame takes the chain on its own, the depth and the intrinsics are done once
+        return self.apply(frames + list(images) if self.keep_plain else frames, gt_depth, intrinsics, flip, crop)
 
     def apply(self, images, gt_depth, intrinsics, flip, crop=None):
-        """The chain for given draws: flip (bool) and crop = (sx, sy, sh, sw, oy, ox) or None."""
+        """The chain behind the colour jitter for given draws: flip (bool) and crop = (sx, sy, sh, sw, oy, ox) or None."""
         if flip:
             images = [np.ascontiguousarray(np.fliplr(im)) for im in images]
             gt_depth = np.ascontiguousarray(np.fliplr(gt_depth))
@@ -116,7 +166,9 @@ def _files(folder, ext):
 class SequenceFolder(data.Dataset):
     """root/scene/{0000000.jpg, 0000000.npy, ..., cam.txt}; train.txt / val.txt list the scenes.
     Yields (tgt_img, gt_depth) -- or (tgt_img, ref_imgs, intrinsics, intrinsics_inv, gt_depth) with `with_refs`, the
-    5-tuple the reference's --unsupervised branch expects but its loader no longer returns."""
+    5-tuple the reference's --unsupervised branch expects but its loader no longer returns.  A transform with
+    `keep_plain` (Transform(color_aug=True, keep_plain=True)) adds a sixth entry, the unjittered frames [tgt, refs...]; every other
+    sample keeps its layout."""
 
     def __init__(self, root, seed=None, train=True, sequence_length=3, transform=None, percentage=1, with_refs=False):
         np.random.seed(seed)
@@ -142,9 +194,12 @@ class SequenceFolder(data.Dataset):
         imgs = [load_as_float(s["tgt"])] + ([load_as_float(r) for r in s["ref_imgs"]] if self.with_refs else [])
         gt = np.load(s["gt_depth"]).astype(np.float32)
         intr = np.copy(s["intrinsics"])
+        n = len(imgs)
         if self.transform is not None:
             imgs, gt, intr = self.transform(imgs, gt, intr)
         if self.with_refs:
+            if getattr(self.transform, "keep_plain", False):     # a sixth entry, the plain frames in the order [tgt, refs...]
+                return imgs[0], imgs[1:n], intr, np.linalg.inv(intr), gt, imgs[n:]
             return imgs[0], imgs[1:], intr, np.linalg.inv(intr), gt
         return imgs[0], gt
 

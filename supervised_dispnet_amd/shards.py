@@ -19,6 +19,13 @@ caller that wants the JPEG loader's exact draws passes its own generator as `fli
 scales and the crop offset from a private `numpy.random.RandomState` seeded like the flip generator (`aug_rng` overrides it), builds the
 windowed Pillow coefficient rows, uploads them with the batch and adjusts the intrinsics; `dn_scale_crop_minmax`, `dn_scale_crop_u8` and
 `dn_scale_crop_depth` then take the place of `dn_u8_normalize_flip` / `dn_flip_w`, again bit-identical to `data.Transform(scale_crop=True)`.
+
+`color_aug=True` adds monodepth2's colour jitter in front of both: per sample the producer thread draws
+`data.draw_colour_jitter` from a third private stream (`colour_rng` overrides it), so neither the flips nor the scale-crop draws of a run
+move when the jitter is switched on; the draws travel as a small table with the batch, and `dn_colour_jitter_sums` +
+`dn_colour_jitter_normalize_flip` take the place of `dn_u8_normalize_flip` (with `scale_crop`: `dn_colour_jitter_u8` writes jittered bytes
+the scale-crop launches read).  `keep_plain=True` also hands out the unjittered frames, as `._dn_plain` of every yielded image tensor --
+what a self-supervised objective compares, while the networks see the jittered ones.  Bit-identical to `data.colour_jitter_u8` (Pillow).
 """
 import json
 import os
@@ -30,8 +37,24 @@ import numpy as np
 import torch
 
 from . import _lib, engine
-from .data import draw_scale_crop, scale_crop_intrinsics
+from .data import draw_colour_jitter, draw_scale_crop, scale_crop_intrinsics
 from .inference import IMAGE_CHUNKS, scale_crop_table
+
+COLOUR_PARAMS = 8                  # DN_COLOUR_PARAMS: int32 per sample {jittered, order, bits of b / c / s, hue shift, 0, 0}
+_COLOUR_STREAM = 0x6A177E12        # xor-ed into the augmentation seed: the jitter draws are a stream of their own
+
+
+def colour_params_row(params, out):
+    """One row of the device table of dn_colour_jitter_* from what data.draw_colour_jitter returned (None: not jittered)."""
+    out[:] = 0
+    if params is None:
+        return out
+    order, b, c, s, shift = params
+    out[0] = 1
+    out[1] = sum(int(o) << (2 * k) for k, o in enumerate(order))
+    out[2:5] = np.array([b, c, s], dtype=np.float32).view(np.int32)       # Image.blend takes the factor as a C float
+    out[5] = int(shift) & 255
+    return out
 
 
 def write_shards(root, out_dir, train=True, sequence_length=3, with_gt=False):
@@ -109,10 +132,12 @@ class ShardLoader(object):
     """Iterable over device-resident, normalised batches.  Yields (tgt_img[B,3,H,W], gt_depth[B,H,W]) or, `with_refs`, the 5-tuple
     (tgt_img, [ref_imgs], intrinsics[B,3,3], intrinsics_inv[B,3,3], gt_depth) of the reference's --unsupervised branch.
     One process per GPU: every rank walks the same shuffled order and keeps its contiguous slice of each global batch
-    (data.RankSampler)."""
+    (data.RankSampler).  `color_aug`: tgt_img / ref_imgs are the colour-jittered frames; with `keep_plain` each of them carries the
+    unjittered one as `._dn_plain`."""
 
     def __init__(self, shards, batch_size, device, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), flip=True, shuffle=True, seed=0,
-                 rank=0, world=1, with_refs=False, drop_last=True, prefetch=2, flip_rng=None, percentage=1, scale_crop=False, aug_rng=None):
+                 rank=0, world=1, with_refs=False, drop_last=True, prefetch=2, flip_rng=None, percentage=1, scale_crop=False, aug_rng=None,
+                 color_aug=False, keep_plain=False, colour_rng=None):
         from .data import RankSampler
         self.set = shards if isinstance(shards, ShardSet) else ShardSet(shards, percentage=percentage, seed=seed)
         self.device = torch.device(device)
@@ -133,6 +158,12 @@ class ShardLoader(object):
         self.aug_rng = aug_rng
         if self.scale_crop and aug_rng is None:
             self.aug_rng = np.random.RandomState(self._aug_seed(0))
+        self.color_aug = bool(color_aug)
+        self.keep_plain = bool(color_aug and keep_plain)
+        self._own_colour_rng = colour_rng is None
+        self.colour_rng = colour_rng
+        if self.color_aug and colour_rng is None:
+            self.colour_rng = np.random.RandomState(self._colour_seed(0))
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.nimg = 1 + (len(self.set.samples[0][1]) if with_refs else 0)
         self._ring, self._slot = [], 0           # pinned staging buffers, reused round-robin once their copy has completed
@@ -147,6 +178,8 @@ class ShardLoader(object):
                                    "fl": torch.empty((self.B,), dtype=torch.uint8).pin_memory(), "ev": None})
                 if self.scale_crop:
                     self._ring[-1]["tb"] = torch.empty((self.B, W + H, 4), dtype=torch.int32).pin_memory()
+                if self.color_aug:
+                    self._ring[-1]["cp"] = torch.empty((self.B, COLOUR_PARAMS), dtype=torch.int32).pin_memory()
         slot = self._ring[self._slot]
         self._slot = (self._slot + 1) % n
         if slot["ev"] is not None:
@@ -159,12 +192,17 @@ class ShardLoader(object):
     def _aug_seed(self, epoch):
         return self._flip_seed(epoch) % (1 << 32)          # RandomState takes 32 bits
 
+    def _colour_seed(self, epoch):
+        return self._aug_seed(epoch) ^ _COLOUR_STREAM
+
     def set_epoch(self, epoch):
         self.sampler.set_epoch(epoch)
         if self._own_rng:
             self.rng = random.Random(self._flip_seed(epoch))
         if self.scale_crop and self._own_aug_rng:
             self.aug_rng = np.random.RandomState(self._aug_seed(epoch))
+        if self.color_aug and self._own_colour_rng:
+            self.colour_rng = np.random.RandomState(self._colour_seed(epoch))
 
     def __len__(self):
         return len(self.sampler)
@@ -194,6 +232,8 @@ class ShardLoader(object):
                 sx, sy, sh, sw, oy, ox = draw_scale_crop(self.aug_rng, H, W)
                 crops.append((sh, sw, oy, ox))
                 k = scale_crop_intrinsics(k, sx, sy, oy, ox)
+            if self.color_aug:                                      # a stream of its own: the two draws above stay what they were
+                colour_params_row(draw_colour_jitter(self.colour_rng), slot["cp"].numpy()[j])
             intr[j] = k
         aug = None
         if self.scale_crop:
@@ -215,20 +255,26 @@ class ShardLoader(object):
                 d_tb = torch.empty(aug[0].shape, dtype=torch.int32, device=self.device)
                 d_tb.copy_(aug[0], non_blocking=True)
                 aug = (d_tb,) + aug[1:]
+            d_cp = None
+            if self.color_aug:
+                d_cp = torch.empty((b, COLOUR_PARAMS), dtype=torch.int32, device=self.device)
+                d_cp.copy_(slot["cp"][:b], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         slot["ev"] = ev
-        return d_u8, d_gt, d_fl, intr, ev, aug
+        return d_u8, d_gt, d_fl, intr, ev, aug, d_cp
 
     def _finish(self, staged):
-        d_u8, d_gt, d_fl, intr, ev, aug = staged
+        d_u8, d_gt, d_fl, intr, ev, aug, d_cp = staged
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ev)
-        for t in (d_u8, d_gt, d_fl):
+        for t in (d_u8, d_gt, d_fl) + ((d_cp,) if d_cp is not None else ()):
             t.record_stream(cur)
         n, b, H, W, _ = d_u8.shape
         imgs = torch.empty((n, b, 3, H, W), dtype=torch.float32, device=self.device)
         st = cur.cuda_stream
+        if d_cp is not None:
+            return self._colour(d_u8, d_gt, d_fl, d_cp, aug, imgs, intr, st)
         if aug is not None:
             return self._batch(imgs, self._scale_crop(d_u8, d_gt, d_fl, aug, imgs, st), intr)
         for i in range(n):
@@ -238,25 +284,60 @@ class ShardLoader(object):
         engine.hbm_call("dn::flip_w_kernel", b * H * W * 8, "dn_flip_w", d_gt.data_ptr(), d_fl.data_ptr(), b, H, W, gt.data_ptr(), st)
         return self._batch(imgs, gt, intr)
 
-    def _batch(self, imgs, gt, intr):
+    def _batch(self, imgs, gt, intr, plain=None):
+        frames = [imgs[i] for i in range(imgs.shape[0])]
+        if plain is not None:                                        # the unjittered frames ride on the jittered ones
+            for i, f in enumerate(frames):
+                f._dn_plain = plain[i]
         if not self.with_refs:
-            return imgs[0], gt
+            return frames[0], gt
         k = torch.from_numpy(intr)
-        return imgs[0], [imgs[i] for i in range(1, imgs.shape[0])], k.to(self.device), torch.from_numpy(np.linalg.inv(intr)).to(self.device), gt
+        return frames[0], frames[1:], k.to(self.device), torch.from_numpy(np.linalg.inv(intr)).to(self.device), gt
+
+    def _colour(self, d_u8, d_gt, d_fl, d_cp, aug, imgs, intr, st):
+        """The jittered path: the luma sums of every frame, then the chain -- into the normalised batch (and the plain one from the same
+        read), or, with scale_crop, into jittered bytes the scale-crop launches read (a second time on the plain bytes for keep_plain)."""
+        n, b, H, W, _ = d_u8.shape
+        # (kernel = None: the entry points pick an instantiation by size and alignment and report its name, dn_last_kernel)
+        sums = torch.empty((n * b, IMAGE_CHUNKS), dtype=torch.int64, device=self.device)
+        plain = torch.empty_like(imgs) if self.keep_plain else None
+        engine.hbm_call(None, 3 * n * b * H * W, "dn_colour_jitter_sums", d_u8.data_ptr(), d_cp.data_ptr(), n, b, H, W,
+                        sums.data_ptr(), st)
+        if aug is None:
+            engine.hbm_call(None, (15 + (12 if plain is not None else 0)) * n * b * H * W, "dn_colour_jitter_normalize_flip",
+                            d_u8.data_ptr(), d_fl.data_ptr(), d_cp.data_ptr(), sums.data_ptr(), n, b, H, W, self.mean_h, self.std_h,
+                            imgs.data_ptr(), plain.data_ptr() if plain is not None else None, st)
+            gt = torch.empty_like(d_gt)
+            engine.hbm_call("dn::flip_w_kernel", b * H * W * 8, "dn_flip_w", d_gt.data_ptr(), d_fl.data_ptr(), b, H, W, gt.data_ptr(), st)
+            return self._batch(imgs, gt, intr, plain)
+        jit = torch.empty_like(d_u8)
+        engine.hbm_call(None, 6 * n * b * H * W, "dn_colour_jitter_u8", d_u8.data_ptr(), d_cp.data_ptr(), sums.data_ptr(),
+                        n, b, H, W, jit.data_ptr(), st)
+        gt = self._scale_crop(jit, d_gt, d_fl, aug, imgs, st)
+        if plain is not None:
+            self._scale_crop(d_u8, None, d_fl, aug, plain, st)
+        return self._batch(imgs, gt, intr, plain)
 
     def _scale_crop(self, d_u8, d_gt, d_fl, aug, imgs, st):
-        """The three launches of the augmented path: partial min / max of every frame and map, all n * b frames, the depth -> gt."""
+        """The three launches of the augmented path: partial min / max of every frame and map, all n * b frames, the depth -> gt
+        (d_gt = None: the frames only, two launches)."""
         d_tb, scaled_hw, taps = aug
         d_tb.record_stream(torch.cuda.current_stream(self.device))
         n, b, H, W, _ = d_u8.shape
         mm_u8 = torch.empty((n * b, IMAGE_CHUNKS, 2), dtype=torch.int32, device=self.device)
-        mm_gt = torch.empty((b, IMAGE_CHUNKS, 2), dtype=torch.float32, device=self.device)
-        gt = torch.empty_like(d_gt)
         hw = scaled_hw.ctypes.data_as(_C.c_void_p)
-        engine.hbm_call("dn::scale_crop_minmax_kernel", (3 * n + 4) * b * H * W, "dn_scale_crop_minmax", d_u8.data_ptr(), d_gt.data_ptr(), n, b,
-                        H, W, mm_u8.data_ptr(), mm_gt.data_ptr(), st)
+        if d_gt is None:
+            engine.hbm_call("dn::scale_crop_minmax_kernel", 3 * n * b * H * W, "dn_scale_crop_minmax", d_u8.data_ptr(), None, n, b, H, W,
+                            mm_u8.data_ptr(), None, st)
+        else:
+            mm_gt = torch.empty((b, IMAGE_CHUNKS, 2), dtype=torch.float32, device=self.device)
+            gt = torch.empty_like(d_gt)
+            engine.hbm_call("dn::scale_crop_minmax_kernel", (3 * n + 4) * b * H * W, "dn_scale_crop_minmax", d_u8.data_ptr(), d_gt.data_ptr(), n, b,
+                            H, W, mm_u8.data_ptr(), mm_gt.data_ptr(), st)
         engine.hbm_call("dn::scale_crop_tile_kernel<unsigned char, 3>", n * b * H * W * 15, "dn_scale_crop_u8", d_u8.data_ptr(), d_fl.data_ptr(),
                         n, b, H, W, mm_u8.data_ptr(), d_tb.data_ptr(), hw, taps, self.mean_h, self.std_h, imgs.data_ptr(), st)
+        if d_gt is None:
+            return None
         engine.hbm_call("dn::scale_crop_tile_kernel<float, 1>", b * H * W * 8, "dn_scale_crop_depth", d_gt.data_ptr(), d_fl.data_ptr(), b, H, W,
                         mm_gt.data_ptr(), d_tb.data_ptr(), hw, taps, gt.data_ptr(), st)
         return gt

@@ -16,6 +16,9 @@ What differs from the reference, on purpose:
     always at the reference's 256x352 crop); it needs --with-gt and refuses --unsupervised and --shards;
   * `--scale-crop` (off by default) adds the reference's RandomScaleCrop to the training samples, on the GPU with --shards
     (DESIGN.md section 14) and in the loader workers otherwise; --dataset nyu and --synthetic refuse it;
+  * `--color-aug` (off by default) adds monodepth2's colour jitter to the training samples, on the GPU with --shards (DESIGN.md
+    section 19) and in the loader workers otherwise: the networks see the jittered frames, the photometric terms of --unsupervised
+    compare the plain ones; --dataset nyu and --synthetic refuse it;
   * `--synthetic N` (extension) trains on N synthetic samples with the statistics of SURVEY.md section 8d, for boxes
     without a dataset; tensorboard / progress-bar logging is replaced by plain prints and the two CSV logs.
 """
@@ -93,6 +96,11 @@ def build_parser():
                    help="train with the reference's RandomScaleCrop behind the flip (custom_transforms.py:73-113: zoom up to 15 %% per axis "
                         "with scipy.misc.imresize, crop back, depth and intrinsics follow); on the GPU with --shards "
                         "(dn_scale_crop_u8 / dn_scale_crop_depth), in the workers otherwise.  Never applied to validation")
+    p.add_argument("--color-aug", action="store_true",
+                   help="train with monodepth2's colour jitter: for half of the samples brightness, contrast and saturation in [0.8, 1.2] and "
+                        "hue in [-0.1, 0.1] in a random order, Pillow's arithmetic (torchvision's ColorJitter on PIL images); on the GPU with "
+                        "--shards (dn_colour_jitter_*), in the workers otherwise.  The networks see the jittered frames; the photometric terms "
+                        "of --unsupervised compare the plain ones.  Never applied to validation")
     p.add_argument("--img-height", type=int, default=128, help="synthetic image height")
     p.add_argument("--img-width", type=int, default=416, help="synthetic image width")
     p.add_argument("--train-pose", action="store_true", help="also optimise PoseExpNet (the reference never does, appendix C-3)")
@@ -226,6 +234,10 @@ def check_dataset_args(args):
         raise SystemExit("--scale-crop augments decoded frames (scene folders or --shards); --synthetic samples are generated normalised")
     if args.scale_crop and args.dataset == "nyu":
         raise SystemExit("--scale-crop is the KITTI / scene-folder augmentation; --dataset nyu runs its own chain (rotate, zoom, colour)")
+    if args.color_aug and args.synthetic > 0:
+        raise SystemExit("--color-aug jitters decoded uint8 frames (scene folders or --shards); --synthetic samples are generated normalised")
+    if args.color_aug and args.dataset == "nyu":
+        raise SystemExit("--color-aug is monodepth2's jitter for KITTI / scene folders; --dataset nyu runs its own chain (rotate, zoom, colour)")
     if args.dataset != "nyu" or args.synthetic > 0:
         return
     if args.shards:
@@ -294,7 +306,8 @@ def main(argv=None):
         if args.shards:
             train_set = None                         # --shards replaces the JPEG train set: do not crawl the scene folders for it
         else:
-            train_set = D.SequenceFolder(args.data, transform=D.Transform(mean, std, flip=True, scale_crop=args.scale_crop), seed=args.seed,
+            train_set = D.SequenceFolder(args.data, transform=D.Transform(mean, std, flip=True, scale_crop=args.scale_crop,
+                                                                          color_aug=args.color_aug, keep_plain=with_refs), seed=args.seed,
                                          train=True,
                                          sequence_length=args.sequence_length, percentage=args.data_amount, with_refs=with_refs)
         if args.with_gt:
@@ -322,7 +335,8 @@ def main(argv=None):
         from supervised_dispnet_amd.shards import ShardLoader
         mean, std = D.normalization(args.imagenet_normalization, args.monodepth2)
         train_loader = ShardLoader(args.shards, per_rank, device, mean=mean, std=std, flip=True, shuffle=True, seed=args.seed, rank=rank,
-                                   world=world, with_refs=with_refs, percentage=args.data_amount, scale_crop=args.scale_crop)
+                                   world=world, with_refs=with_refs, percentage=args.data_amount, scale_crop=args.scale_crop,
+                                   color_aug=args.color_aug, keep_plain=with_refs)
         train_sampler = train_loader                 # set_epoch() reshuffles (and re-seeds the flip draws)
         if rank == 0:
             print("{} samples found in {} train scenes (shards)".format(len(train_loader.set), len(train_loader.set.scenes)))
@@ -461,11 +475,19 @@ def _homogeneous(m):
 
 def _to_device_batch(batch, device, unsupervised, homogeneous=False):
     if unsupervised:
-        tgt, refs, intr, intr_inv, gt = batch
+        tgt, refs, intr, intr_inv, gt = batch[:5]
         if homogeneous:
             intr, intr_inv = _homogeneous(intr), _homogeneous(intr_inv)
-        return (tgt.to(device, non_blocking=True), [r.to(device, non_blocking=True) for r in refs],
-                torch.as_tensor(intr).float().to(device), torch.as_tensor(intr_inv).float().to(device), gt.to(device, non_blocking=True))
+        frames = [tgt] + list(refs)
+        # --color-aug: the unjittered frames ride on the jittered ones as ._dn_plain (the shard loader hands them out that way, .to() of a
+        # device tensor is the tensor itself; the JPEG loader's sixth entry holds them in the order [tgt, refs...])
+        plain = list(batch[5]) if len(batch) > 5 else [getattr(f, "_dn_plain", None) for f in frames]
+        frames = [f.to(device, non_blocking=True) for f in frames]
+        for f, p in zip(frames, plain):
+            if p is not None:
+                f._dn_plain = p.to(device, non_blocking=True)
+        return (frames[0], frames[1:], torch.as_tensor(intr).float().to(device), torch.as_tensor(intr_inv).float().to(device),
+                gt.to(device, non_blocking=True))
     tgt, gt = batch
     return tgt.to(device, non_blocking=True), None, None, None, gt.to(device, non_blocking=True)
 
@@ -623,19 +645,27 @@ class TapedTrainer(object):
             return None
 
 
-def min_reprojection_objective(args, LF, disp_net, pose_cnn, tgt_img, ref_imgs, K, inv_K):
+def plain_frames(tgt_img, ref_imgs):
+    """The frames the photometric terms compare: the unjittered ones a --color-aug loader hung on the batch, else the batch itself."""
+    return getattr(tgt_img, "_dn_plain", tgt_img), [getattr(r, "_dn_plain", r) for r in ref_imgs]
+
+
+def min_reprojection_objective(args, LF, disp_net, pose_cnn, tgt_img, ref_imgs, K, inv_K, net_tgt=None, net_refs=None):
     """monodepth2's training objective for one batch.  The pose network runs ONCE on the F * B stacked pairs in temporal order --
     [ref, tgt] for a frame before the target (its pose is inverted), [tgt, ref] for one after it; it has no batch statistics, so this
-    equals F calls -- and the loss reads the frame-major result [F, B, 6] through its strides: no slice, no copy."""
+    equals F calls -- and the loss reads the frame-major result [F, B, 6] through its strides: no slice, no copy.
+    net_tgt / net_refs: what the two networks see when that is not what the loss compares (--color-aug: the jittered frames)."""
     B, F = tgt_img.shape[0], len(ref_imgs)
     earlier = [f < F // 2 for f in range(F)]
-    pairs = torch.cat([torch.cat([r, tgt_img] if e else [tgt_img, r], 1) for r, e in zip(ref_imgs, earlier)], 0)
+    net_tgt = tgt_img if net_tgt is None else net_tgt
+    net_refs = ref_imgs if net_refs is None else net_refs
+    pairs = torch.cat([torch.cat([r, net_tgt] if e else [net_tgt, r], 1) for r, e in zip(net_refs, earlier)], 0)
     axisangle, _translation = pose_cnn(pairs)
     base = axisangle._dn_pose_base                                   # dense [F * B, 6, 1, 1]
     v = base.view(F, B, 1, 6).permute(1, 0, 2, 3)                    # [B, F, 1, 6]: batch stride 6, frame stride 6 B
     aa, tr = v[..., :3], v[..., 3:]
     aa._dn_pose_base = tr._dn_pose_base = base
-    return LF.monodepth2_loss(tgt_img, ref_imgs, disp_net(tgt_img), K, inv_K, (aa, tr, earlier), min_depth=args.min_depth,
+    return LF.monodepth2_loss(tgt_img, ref_imgs, disp_net(net_tgt), K, inv_K, (aa, tr, earlier), min_depth=args.min_depth,
                               max_depth=args.max_depth, scaled_disp=True, automask=not args.no_automask,
                               smoothness=args.smooth_loss_weight, align_corners=args.legacy_align_corners)
 
@@ -661,7 +691,9 @@ def train(ctx, loader, disp_net, pose_exp_net, optimizer, epoch_size, n_iter):
         data_time.update(time.time() - end)
         tgt_img, ref_imgs, intrinsics, intrinsics_inv, gt_depth = _to_device_batch(batch, device, args.unsupervised, args.min_reprojection)
         if args.min_reprojection:
-            loss = min_reprojection_objective(args, LF, disp_net, ctx["pose_cnn"], tgt_img, ref_imgs, intrinsics, intrinsics_inv)
+            plain_tgt, plain_refs = plain_frames(tgt_img, ref_imgs)
+            loss = min_reprojection_objective(args, LF, disp_net, ctx["pose_cnn"], plain_tgt, plain_refs, intrinsics, intrinsics_inv,
+                                              net_tgt=tgt_img, net_refs=ref_imgs)
             optimizer.zero_grad()
             loss.backward()
             if reducer is not None:
@@ -717,7 +749,8 @@ def train(ctx, loader, disp_net, pose_exp_net, optimizer, epoch_size, n_iter):
         if not args.unsupervised:
             loss_1 = supervised_loss(args, LF, gt_depth, depth, pred_ord, target_c)
         else:
-            loss_1 = LF.photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_inv, depth, explainability_mask, pose,
+            plain_tgt, plain_refs = plain_frames(tgt_img, ref_imgs)          # the networks above saw the jittered frames (--color-aug)
+            loss_1 = LF.photometric_reconstruction_loss(plain_tgt, plain_refs, intrinsics, intrinsics_inv, depth, explainability_mask, pose,
                                                         args.rotation_mode, args.padding_mode, align_corners=args.legacy_align_corners)
         loss_2 = LF.explainability_loss(explainability_mask) if w2 > 0 else 0
         # the reference evaluates the smoothness term unconditionally and multiplies it by -s (train.py:483-488);
