@@ -384,6 +384,18 @@ int dn_resize_bilinear_bwd(const float* dout, int32_t N, int32_t IH, int32_t IW,
 /* out[n][c] = scale * mean over pixels of x[n][p][c] (NHWC): pose = 0.01 * pose_pred(...).mean(3).mean(2), models/PoseExpNet.py:73-75 */
 int dn_spatial_mean_fwd(const float* x, int32_t N, int64_t HW, int32_t C, float scale, float* out, dn_stream_t stream);
 int dn_spatial_mean_bwd(const float* dout, int32_t N, int64_t HW, int32_t C, float scale, float* dx, dn_stream_t stream);
+/* Tail of monodepth2's PoseDecoder, scale * mean_hw(conv1x1(x) + bias), as mean then product (csrc/dn_posetail.hip).
+ * x [P][HW][C] fp32 NHWC, 16-byte aligned; w [O][C]; bias [O].  Only the first O_used outputs are produced:
+ *   mean[p][c] = (1 / HW) sum_s x[p][s][c]                                   (kept for the backward)
+ *   out[p][o]  = scale * (bias[o] + sum_c w[o][c] * mean[p][c]),  o < O_used   (dense [P][O_used])
+ * Backward, one launch: dx[p][s][c] = (scale / HW) sum_{o < O_used} dout[p][o] w[o][c] (the plain gradient with respect to x),
+ *   dw[o][c] = scale * sum_p dout[p][o] mean[p][c], dbias[o] = scale * sum_p dout[p][o], sums over p in index order; rows o >= O_used of
+ *   dw [O][C] and dbias [O] are written as zeros.  Deterministic: fixed summation orders, no float atomics.
+ * DN_ERR_BAD_ARG unless C % 64 == 0, C <= 512, 1 <= O_used <= O <= 24, HW >= 1, P >= 1. */
+int dn_pose_tail_fwd(const float* x, const float* w, const float* bias, int32_t P, int64_t HW, int32_t C, int32_t O, int32_t O_used,
+                     float scale, float* mean, float* out, dn_stream_t stream);
+int dn_pose_tail_bwd(const float* dout, const float* mean, const float* w, int32_t P, int64_t HW, int32_t C, int32_t O, int32_t O_used,
+                     float scale, float* dx, float* dw, float* dbias, dn_stream_t stream);
 /* y = 1/x (train.py:445); dx = -dy * y*y */
 int dn_reciprocal_fwd(const float* x, float* y, int64_t n, dn_stream_t stream);
 int dn_reciprocal_bwd(const float* dy, const float* y, float* dx, int64_t n, dn_stream_t stream);

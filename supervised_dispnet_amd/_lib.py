@@ -13,7 +13,7 @@ LIB_PATH = pathlib.Path(os.environ.get("DISPNET_HIP_LIB", _PKG / "libdispnet_hip
 # ABI version this binding was written against (include/dispnet_hip.h: dn_version(), bumped on any signature / struct change).
 # load() refuses a library that reports anything else: a stale .so (DISPNET_HIP_LIB, a build that did not re-run) would otherwise
 # read struct fields past the end of what this binding fills in and mis-marshal arguments -- silent memory corruption, not an error.
-EXPECTED_ABI = 23
+EXPECTED_ABI = 24
 
 DN_MAX_OPERANDS = 3
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_ELU, ACT_SIGMOID_AFFINE = 0, 1, 2, 3, 4
@@ -120,6 +120,8 @@ SIGNATURES = {
     "dn_sub_div": (C.c_int, [_vp, _i64, _f, _f, _vp, _vp]),
     "dn_spatial_mean_fwd": (C.c_int, [_vp, _i32, _i64, _i32, _f, _vp, _vp]),
     "dn_spatial_mean_bwd": (C.c_int, [_vp, _i32, _i64, _i32, _f, _vp, _vp]),
+    "dn_pose_tail_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _f, _vp, _vp, _vp]),
+    "dn_pose_tail_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp]),
     "dn_upsample2x_bilinear_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dn_upsample2x_bilinear_bwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "dn_reciprocal_fwd": (C.c_int, [_vp, _vp, _i64, _vp]),

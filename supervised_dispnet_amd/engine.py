@@ -1604,6 +1604,46 @@ def block_spatial_mean(tape, x, scale=1.0):
     return out
 
 
+def block_pose_tail(tape, sink, x, layer, o_used, scale):
+    """[N,H,W,C] -> dense [N,1,1,o_used] = scale * mean over H,W of the first o_used channels of the 1x1 conv `layer` (+ bias), as the mean
+    followed by the product: the end of monodepth2's PoseDecoder (reference networks/pose_decoder.py:43-49) in one launch per direction
+    (csrc/dn_posetail.hip).  The rows of the layer past o_used get an exactly zero gradient; the parameter gradients go where a
+    ConvLayer's go (GradSink: the arena view in place, reducer notified)."""
+    m = layer.m
+    if x.scale is not None or x.no_relu:
+        raise RuntimeError("block_pose_tail expects a plain activation")
+    if (layer.R, layer.S, layer.stride, layer.pad, layer.Cin) != (1, 1, 1, 0, x.C) or layer.transposed or m.bias is None:
+        raise RuntimeError("block_pose_tail expects a biased 1x1 / stride-1 nn.Conv2d over the activation's %d channels" % x.C)
+    if x.strides != (x.H * x.W * x.C, x.W * x.C, x.C, 1):
+        raise RuntimeError("block_pose_tail expects a dense NHWC activation")
+    w = m.weight if m.weight.is_contiguous() else m.weight.contiguous()
+    HW, O = x.H * x.W, layer.Cout
+    mean = torch.empty((x.N, x.C), dtype=torch.float32, device=x.t.device)
+    o_t = torch.empty((x.N, 1, 1, o_used), dtype=torch.float32, device=x.t.device)
+    hbm_call("dn::pose_tail_fwd_kernel", 4 * (x.rows * x.C + O * x.C + x.N * (x.C + o_used)), "dn_pose_tail_fwd", x.t.data_ptr(),
+             w.data_ptr(), m.bias.data_ptr(), x.N, HW, x.C, O, o_used, scale, mean.data_ptr(), o_t.data_ptr(), _stream())
+    out = Act(o_t, x.N, 1, 1, o_used)
+
+    def backward():
+        if out.grad is None:
+            sink.put_none(m.weight)
+            sink.put_none(m.bias)
+            return
+        if x.grad is not None:
+            raise RuntimeError("block_pose_tail: single-consumer input expected")
+        x.grad, x.bn_sums = x.new_like(), None
+        dw, db = sink.dest_or_new(m.weight), sink.dest_or_new(m.bias)
+        hbm_call("dn::pose_tail_bwd_kernel", 4 * (x.rows * x.C + 2 * O * x.C + x.N * (x.C + o_used)), "dn_pose_tail_bwd",
+                 out.grad.data_ptr(), mean.data_ptr(), w.data_ptr(), x.N, HW, x.C, O, o_used, scale, x.grad.data_ptr(), dw.data_ptr(),
+                 db.data_ptr(), _stream())
+        sink.put(m.weight, dw)
+        sink.put(m.bias, db)
+        out.grad = None
+
+    tape.push(backward)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- FCRN / ASPP blocks (SURVEY 8 f-4)
 def block_bn_plain(tape, y):
     """Materialise bn(y) WITHOUT ReLU of a block_conv_bn(..., relu=False) result as a plain activation (FCRN: `x = self.bn2(self.conv2(x))`

@@ -118,8 +118,17 @@ def build_parser():
     p.add_argument("--min-reprojection", action="store_true",
                    help="with --unsupervised --monodepth2: train with monodepth2's own objective (loss_functions.monodepth2_loss: per-pixel "
                         "minimum reprojection with automasking over the decoder's four scales + edge-aware smoothness weighted by -s) and "
-                        "networks.PoseCNN on the frame pairs, both networks in the optimizer; --pretrained-exppose then names a monodepth2 "
-                        "pose.pth, and the pose checkpoint takes the place of the PoseExpNet one")
+                        "the --pose-model network (default networks.PoseCNN) on the frame pairs, both networks in the optimizer; "
+                        "--pretrained-exppose then names a PoseCNN pose.pth (with --pose-model resnet18: a released monodepth2 model's "
+                        "folder), and the pose checkpoint takes the place of the PoseExpNet one")
+    p.add_argument("--pose-model", choices=["posecnn", "resnet18"], default="posecnn",
+                   help="--min-reprojection: the pose network.  posecnn: networks.PoseCNN (--pretrained-exppose names a PoseCNN pose.pth "
+                        "FILE).  resnet18: networks.PoseResnet(18), monodepth2's default `separate_resnet` -- the one every released "
+                        "monodepth2 model was trained with; --pretrained-exppose then names the model's FOLDER and loads its "
+                        "pose_encoder.pth + pose.pth, --pretrained-encoder starts its pair encoder from ImageNet as monodepth2 does, and "
+                        "every checkpoint also writes a pose_mono2/ folder in that two-file layout (pose_mono2_best/ when best) that "
+                        "--pretrained-exppose takes again.  Its BatchNorms always train: --freeze-bn and the BatchNorm freezing of "
+                        "--diff-lr apply to the depth network only")
     p.add_argument("--min-depth", type=float, default=0.1, help="--min-reprojection: monodepth2's min_depth")
     p.add_argument("--max-depth", type=float, default=100.0, help="--min-reprojection: monodepth2's max_depth")
     p.add_argument("--no-automask", action="store_true", help="--min-reprojection: without the identity-reprojection terms")
@@ -230,6 +239,11 @@ def check_dataset_args(args):
     """Settings the NYU Depth v2 loader cannot serve, refused before anything touches the GPU (one line each)."""
     if args.min_reprojection and not (args.unsupervised and args.monodepth2):
         raise SystemExit("--min-reprojection is monodepth2's objective: it needs --unsupervised --monodepth2")
+    if args.pose_model != "posecnn" and not args.min_reprojection:
+        raise SystemExit("--pose-model %s is the pose network of monodepth2's objective: it needs --min-reprojection" % args.pose_model)
+    if args.pose_model == "resnet18" and args.pretrained_exp_pose and not os.path.isdir(args.pretrained_exp_pose):
+        raise SystemExit("--pose-model resnet18: --pretrained-exppose names a monodepth2 model FOLDER (pose_encoder.pth + pose.pth), and "
+                         "'%s' is %s" % (args.pretrained_exp_pose, "a file" if os.path.isfile(args.pretrained_exp_pose) else "not a folder"))
     if args.scale_crop and args.synthetic > 0:
         raise SystemExit("--scale-crop augments decoded frames (scene folders or --shards); --synthetic samples are generated normalised")
     if args.scale_crop and args.dataset == "nyu":
@@ -362,10 +376,18 @@ def main(argv=None):
     pose_cnn = None
     if args.min_reprojection:
         # monodepth2's pose network on frame pairs; PoseExpNet stays what validation without ground truth runs, untrained
-        pose_cnn = networks.PoseCNN(num_input_frames=2).to(device)
-        if args.pretrained_exp_pose:
-            state = torch.load(args.pretrained_exp_pose, map_location=device)
-            pose_cnn.load_state_dict(state.get("state_dict", state))          # a monodepth2 pose.pth is the bare state_dict
+        if args.pose_model == "resnet18":
+            # monodepth2's default (separate_resnet): what its released pose_encoder.pth + pose.pth hold
+            pose_cnn = networks.PoseResnet(18, pretrained=args.pretrained_encoder).to(device)
+            if args.pretrained_exp_pose:
+                pose_cnn.load_monodepth2(args.pretrained_exp_pose)
+        else:
+            pose_cnn = networks.PoseCNN(num_input_frames=2).to(device)
+            if args.pretrained_exp_pose:
+                state = torch.load(args.pretrained_exp_pose, map_location=device)
+                pose_cnn.load_state_dict(state.get("state_dict", state))          # a monodepth2 pose.pth is the bare state_dict
+        if rank == 0:
+            print("=> pose model: {} ({})".format(args.pose_model, type(pose_cnn).__name__))
         pose_exp_net.init_weights()
     elif args.pretrained_exp_pose:
         pose_exp_net.load_state_dict(torch.load(args.pretrained_exp_pose, map_location=device)["state_dict"], strict=False)
@@ -456,6 +478,11 @@ def main(argv=None):
                             {"epoch": epoch + 1, "state_dict": disp_net.state_dict(), "optimizer": optimizer.state_dict()},
                             {"epoch": epoch + 1, "state_dict": (pose_cnn if pose_cnn is not None else pose_exp_net).state_dict()},
                             is_best, epoch, record=args.record)
+            if hasattr(pose_cnn, "save_monodepth2"):
+                # monodepth2's two-file layout next to the checkpoint: what --pose-model resnet18 --pretrained-exppose continues from
+                pose_cnn.save_monodepth2(os.path.join(save_path, "pose_mono2"))
+                if is_best:
+                    shutil.copytree(os.path.join(save_path, "pose_mono2"), os.path.join(save_path, "pose_mono2_best"), dirs_exist_ok=True)
             with open(os.path.join(save_path, args.log_summary), "a") as f:
                 csv.writer(f, delimiter="\t").writerow([train_loss, decisive])
     if ctx.get("tape") is not None:
@@ -652,8 +679,8 @@ def plain_frames(tgt_img, ref_imgs):
 
 def min_reprojection_objective(args, LF, disp_net, pose_cnn, tgt_img, ref_imgs, K, inv_K, net_tgt=None, net_refs=None):
     """monodepth2's training objective for one batch.  The pose network runs ONCE on the F * B stacked pairs in temporal order --
-    [ref, tgt] for a frame before the target (its pose is inverted), [tgt, ref] for one after it; it has no batch statistics, so this
-    equals F calls -- and the loss reads the frame-major result [F, B, 6] through its strides: no slice, no copy.
+    [ref, tgt] for a frame before the target (its pose is inverted), [tgt, ref] for one after it; PoseCNN has no batch statistics, so this
+    equals F calls (PoseResnet's BatchNorms take theirs over all F * B pairs) -- and the loss reads the frame-major result [F, B, 6] through its strides: no slice, no copy.
     net_tgt / net_refs: what the two networks see when that is not what the loss compares (--color-aug: the jittered frames)."""
     B, F = tgt_img.shape[0], len(ref_imgs)
     earlier = [f < F // 2 for f in range(F)]
