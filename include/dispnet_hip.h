@@ -871,6 +871,36 @@ int dn_resize_u8(const uint8_t* frames, const int32_t* hw, const int64_t* off, i
                  const int32_t* tab_idx, int32_t max_taps, uint8_t* out_u8, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Pose evaluation on the device (eval_pose.py): odometry ATE / RE of the pose networks.
+ * dn_snippet_gather: dst[n][3k + c][y][x] = ((ring[idx[n][k] mod R][y][x][c] / 255) - mean[c]) / std[c], IEEE fp32 in exactly that order
+ * (dn_eval_normalize's rule).  ring = uint8[R][H][W][3], the resident resized frames, slot = frame index mod R (a negative index wraps
+ * too: no table reads outside the ring); idx = int32[N][K] on the device; dst = fp32[N][3K][H][W], dense, the channel-concatenated
+ * snippets one forward takes as ONE operand.  mean_host / std_host: 3 floats each on the host.  Any H, W >= 1: where H * W is a multiple
+ * of 4 (and ring is 4-byte, dst 16-byte aligned) a thread moves 4 pixels as three words in and three float4 out, otherwise pixel by pixel.
+ * dn_pose_eval_sfm (SfMLearner's test_pose.py): pose = fp32[N][L-1][6], the (tx, ty, tz, rx, ry, rz) of the reference frames in temporal
+ * order; a zero row is inserted at L / 2 (the target), P[L][6].  M_k = pose_vec2mat(P_k) as [R|t] in fp64 FROM the fp32 vector
+ * (rotation_mode 0: Rx Ry Rz, 1: the (1, x, y, z) quaternion normalised), R_k = inv(M_k[:, :3]), t_k = -R_k M_k[:, 3],
+ * F_k = [M_0r R_k | M_0r t_k + M_0t].  gt = fp64[N][L][3][4], the compensated ground-truth poses.  With p = F:
+ * s = sum(g_t . p_t) / sum(p_t . p_t) over all L translations, ATE = |g_t - s p_t|_2 / L,
+ * RE = (1/L) sum_k atan2(|(D01 - D10, D12 - D21, D02 - D20)|_2, trace(D) - 1), D = g_kr inv(p_kr).  out = fp64[N][2] {ATE, RE}.
+ * 2 <= L <= DN_POSE_EVAL_MAX_L.  All-zero predicted translations give ATE = 0 / 0 = NaN, as numpy does.
+ * dn_pose_eval_mono2 (monodepth2's evaluate_pose.py): pose = fp32[P][6], (axisangle, translation) of the pairs (i, i + 1);
+ * T_i = transformation_from_parameters(invert = False) = [Rodrigues(axisangle / (|axisangle| + 1e-7)) | translation] in fp64 from the
+ * fp32 numbers; Q = fp64[P][4][4], the ground-truth local transforms (rows 0..2 are read).  Window i = 0 .. P-1 takes transforms
+ * i .. min(i + track - 1, P) - 1 (shorter at the end): both trajectories start at the origin with C_0 = I, C_{j+1} = C_j T,
+ * xyz_{j+1} = C_{j+1}[:3, 3]; s = sum(gt . pred) / sum(pred . pred); out[i] = sqrt(sum((s pred - gt)^2)) / points.  out = fp64[P].
+ * 2 <= track <= DN_POSE_EVAL_MAX_TRACK (the original: 5).
+ * Both metric kernels: one thread per snippet / window, fp64 without contraction, every sum in index order, no atomics: two runs are
+ * bit-identical.  Every argument is checked before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DN_POSE_EVAL_MAX_L 33
+#define DN_POSE_EVAL_MAX_TRACK 64
+int dn_snippet_gather(const uint8_t* ring, int32_t R, const int32_t* idx, int32_t N, int32_t K, int32_t H, int32_t W, const float* mean_host,
+                      const float* std_host, float* dst, dn_stream_t stream);
+int dn_pose_eval_sfm(const float* pose, int32_t rotation_mode, const double* gt, int32_t N, int32_t L, double* out, dn_stream_t stream);
+int dn_pose_eval_mono2(const float* pose, const double* Q, int32_t P, int32_t track, double* out, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Velodyne clouds -> sparse depth maps (reference data/kitti_raw_loader.py:243-300), a batch per call.
  * points = fp32[total_points][4], the .bin files back to back as they are (column 3 is ignored and taken as 1.0; 16-byte aligned);
  * pt_off = int64[B + 1] on the device, frame b owns points [pt_off[b], pt_off[b + 1]); M = fp64[B][12] on the device, the frame's 3 x 4
