@@ -10,8 +10,17 @@
 --device-resize  with --eval-batch on KITTI: the frames are uploaded as they are and byte-scaled, resized and normalised on the device
                  (dn_imresize_u8; bit for bit the host resize).  NYU and --no-resize keep the host path.
 --readers N      host threads (default 4, at most 16) that read framework[j] -- image, velodyne projection, mask -- ahead of the GPU.
+--protocol P     reference (the default): test_disp.py's chain, as above.  monodepth2: the chain of monodepth2's evaluate_depth.py, the one
+                 its published tables come from -- the disparity is resized bilinearly to the ground-truth size
+                 and inverted, the median ratio (--mono / --unsupervised) or x5.4 (--stereo) is applied FIRST and the result clamped to
+                 [1e-3, 80] LAST, and the median and spread of the ratios are printed.  With --eval-batch on the device
+                 (csrc/dn_eval_mono2.hip); without, per image in numpy (evaluation.mono2_evaluate_sample).  KITTI only; no SID network,
+                 no --error.
+--post-process   with --protocol monodepth2: the prediction is averaged with that of the mirrored frame (one forward at 2N), the "+pp"
+                 rows of monodepth2's tables.
 
-The printed lines, the returned mean errors and predictions.npy are those of test_disp.py.  --error (the worst-300-pixel report) stays
+The printed lines, the returned mean errors and predictions.npy are those of test_disp.py (--protocol monodepth2 keeps the layout, puts
+its own numbers in and adds the line on the scaling ratios in the median mode; predictions.npy stays 1 / disp at network resolution).  --error (the worst-300-pixel report) stays
 on the per-image host chain and refuses --eval-batch.  The PoseNet-scaled evaluation (--pretrained-posenet) and the --pic comparison
 plots are outside this path, as they are outside test_disp.py's.
 
@@ -31,7 +40,7 @@ if ROOT not in sys.path:
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 import test_disp  # noqa: E402  (the reference's command line: parser, network construction, the per-image chain)
-from supervised_dispnet_amd.evaluation import prefetched  # noqa: E402
+from supervised_dispnet_amd.evaluation import check_protocol, prefetched  # noqa: E402
 
 MAX_READERS = 16
 
@@ -42,6 +51,10 @@ def add_flags(p):
     p.add_argument("--device-resize", action="store_true",
                    help="with --eval-batch on KITTI: upload the raw frames and resize them on the device (dn_imresize_u8) instead of on the host")
     p.add_argument("--readers", default=4, type=int, metavar="N", help="host threads that read ahead for --eval-batch (at most 16)")
+    p.add_argument("--protocol", default="reference", choices=["reference", "monodepth2"],
+                   help="reference: test_disp.py's chain; monodepth2: evaluate_depth.py's (bilinear resize of the disparity, scale, then clamp)")
+    p.add_argument("--post-process", action="store_true",
+                   help="with --protocol monodepth2: average the prediction with that of the mirrored frame (the '+pp' rows of its tables)")
     return p
 
 
@@ -59,6 +72,12 @@ def parse_args(argv=None):
         raise SystemExit("eval_disp.py: --device-resize belongs to the batched chain; add --eval-batch N")
     if args.eval_batch and args.error:
         raise SystemExit("eval_disp.py: --error (the worst-300-pixel report) runs on the per-image host chain; drop --eval-batch")
+    if args.protocol == "monodepth2" and args.error:
+        raise SystemExit("eval_disp.py: --error (the worst-300-pixel report) belongs to the reference's chain; drop --protocol monodepth2")
+    try:
+        check_protocol(args.protocol, args.post_process, args.gt_type, args.network)
+    except ValueError as e:
+        raise SystemExit("eval_disp.py: {}".format(e))
     args.readers = max(1, min(MAX_READERS, args.readers))
     return args
 
@@ -70,12 +89,12 @@ def host_chain_argv(argv):
 
 
 def evaluate_batched(args, disp_net, framework, device, min_depth, max_depth):
-    """-> (errors float32 [7, n], predictions [n, h, w] with --output-dir, else None) through the DeviceEvaluator, --eval-batch images at
-    a time, while --readers threads read ahead."""
+    """-> (errors float32 [7, n], predictions [n, h, w] with --output-dir, else None, the scale of every image float32 [n]) through the
+    DeviceEvaluator, --eval-batch images at a time, while --readers threads read ahead."""
     from supervised_dispnet_amd.evaluation import DeviceEvaluator
     evaluator = DeviceEvaluator(args, disp_net, device, min_depth, max_depth)
     n = len(framework)
-    errors = np.zeros((7, n), np.float32)
+    errors, ratios = np.zeros((7, n), np.float32), np.zeros(n, np.float32)
     predictions, batch = None, []
     for j, sample in enumerate(prefetched(framework, n, args.readers, 2 * args.eval_batch + args.readers)):
         batch.append(sample)
@@ -83,21 +102,38 @@ def evaluate_batched(args, disp_net, framework, device, min_depth, max_depth):
             j0 = j + 1 - len(batch)
             errs, depths = evaluator.evaluate(batch)
             errors[:, j0:j + 1] = errs
+            ratios[j0:j + 1] = evaluator.scales
             if args.output_dir is not None:
                 if predictions is None:
                     predictions = np.zeros((n,) + depths[0].shape)
                 predictions[j0:j + 1] = np.stack(depths)
             batch = []
-    return errors, predictions
+    return errors, predictions, ratios
+
+
+def evaluate_per_image(args, disp_net, framework, device, min_depth, max_depth):
+    """The same three results from the per-image host chain of --protocol monodepth2 (evaluation.mono2_evaluate_sample): what runs
+    without --eval-batch, since test_disp.main knows its own chain only."""
+    from supervised_dispnet_amd.evaluation import mono2_evaluate_sample
+    n = len(framework)
+    errors, ratios = np.zeros((7, n), np.float32), np.zeros(n, np.float32)
+    predictions = None
+    for j in range(n):
+        errors[:, j], ratios[j], depth = mono2_evaluate_sample(args, disp_net, framework[j], device, min_depth, max_depth, args.post_process)
+        if args.output_dir is not None:
+            if predictions is None:
+                predictions = np.zeros((n,) + depth.shape)
+            predictions[j] = depth
+    return errors, predictions, ratios
 
 
 @torch.no_grad()
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse_args(argv)
-    if not args.eval_batch:
+    if not args.eval_batch and args.protocol == "reference":
         return test_disp.main(host_chain_argv(argv))
-    # the set-up of test_disp.main, then the batched loop
+    # the set-up of test_disp.main, then the batched loop (or, under --protocol monodepth2 without --eval-batch, its per-image host chain)
     if not torch.cuda.is_available():
         raise SystemExit("eval_disp.py drives the MI355X HIP path; no GPU is visible (there is no CPU fallback)")
     device = torch.device("cuda")
@@ -131,8 +167,12 @@ def main(argv=None):
         min_depth, max_depth = 1e-3, 10
         framework = KE.NyuTestFramework(args.dataset_dir, min_depth=min_depth, max_depth=max_depth)
     print("{} files to test".format(len(framework)))
-    errors, predictions = evaluate_batched(args, disp_net, framework, device, min_depth, max_depth)
+    run = evaluate_batched if args.eval_batch else evaluate_per_image
+    errors, predictions, ratios = run(args, disp_net, framework, device, min_depth, max_depth)
     mean_errors = errors.mean(1)
+    if args.protocol == "monodepth2" and (args.unsupervised or args.mono):        # evaluate_depth.py's line on the median ratios
+        med = np.median(ratios)
+        print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
     names = ["abs_rel", "sq_rel", "rms", "log_rms", "a1", "a2", "a3"]
     print("Results with scale factor determined by GT/prediction ratio (like the original paper) : ")
     print("{:>10}, {:>10}, {:>10}, {:>10}, {:>10}, {:>10}, {:>10}".format(*names))

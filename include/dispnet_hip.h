@@ -835,6 +835,35 @@ int dn_eval_errors(const float* gt, const float* pred, const uint8_t* mask, cons
                    int32_t scale_mode, float fixed_scale, float* out, dn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * monodepth2's depth evaluation on the device (evaluate_depth.py; eval_disp.py --protocol monodepth2).
+ * disp = the network's eval-mode disparity at network resolution, fp32.  Every step below is fp64 arithmetic on the fp32 inputs, without
+ * contraction, and rounds to fp32 exactly once.
+ * dn_mono2_post_process (batch_post_process_disparity): disp = fp32[2B][h][w]; planes B .. 2B-1 are the predictions for the horizontally
+ * mirrored frames and are read mirrored (there is no un-flip pass); out = fp32[B][h][w], out != disp, w >= 2.  Per pixel (y, x):
+ *     l = x / (w - 1);  lm(x) = 1 - clip(20 * (l - 0.05), 0, 1);  rm(x) = lm(w - 1 - x);
+ *     L = disp[b][y][x];  R = disp[B + b][y][w - 1 - x];  out = rm * L + lm * R + (1 - lm - rm) * (0.5 * (L + R)).
+ * dn_bilinear_recip_ragged: disp = fp32[B][h][w] resized bilinearly to a per-image size (H_b, W_b), then inverted; cv2 INTER_LINEAR /
+ * F.interpolate(align_corners=False) geometry: half-pixel centres, replicated edges, no antialiasing when shrinking.  Per axis, output
+ * index o, input length n, output length O:
+ *     s = (o + 0.5) * (n / O) - 0.5;  i0 = floor(s);  f = s - i0;  i0 < 0: i0 = 0, f = 0;  i0 >= n - 1: i0 = n - 1, f = 0;
+ *     i1 = min(i0 + 1, n - 1).
+ * top = (1 - fx) * d[y0][x0] + fx * d[y0][x1], bot the same on row y1, value = (1 - fy) * top + fy * bot, out = fp32(1 / value): equal
+ * sizes give exactly fp32(1 / disp).  out_hw = int32[B][2] {H_b, W_b} and out_off = int64[B] (element offsets) on the device, the ragged
+ * layout of dn_zoom3_clip: image b is H_b x W_b fp32 at out + out_off[b], nothing is written between the images; max_h / max_w: the
+ * largest H_b / W_b of the batch (sizes the grid).  Any h, w >= 1 and H_b, W_b >= 1; B <= 65535.  Four consecutive outputs are stored
+ * as 16 bytes where out + out_off[b] is 16-byte aligned.
+ * dn_eval_errors_clamp: dn_eval_errors (same arguments, same selection and sums, same out = float[B][8] with the scale in column 7)
+ * in monodepth2's order: the scale -- in mode 2 the fp32 ratio of the medians of gt and of the UNCLAMPED pred over the mask -- is applied
+ * first, p = min(max(fp32(pred * scale), lo), hi) second, then the metrics of (gt, p).  0 < lo <= hi.  Masked gt and pred must be
+ * positive.
+ * ------------------------------------------------------------------------------------------------------------ */
+int dn_mono2_post_process(const float* disp, int32_t B, int32_t h, int32_t w, float* out, dn_stream_t stream);
+int dn_bilinear_recip_ragged(const float* disp, int32_t B, int32_t h, int32_t w, const int32_t* out_hw, const int64_t* out_off, int32_t max_h,
+                             int32_t max_w, float* out, dn_stream_t stream);
+int dn_eval_errors_clamp(const float* gt, const float* pred, const uint8_t* mask, const int64_t* off, const int32_t* npix, int32_t B,
+                         int32_t scale_mode, float fixed_scale, float lo, float hi, float* out, dn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Image arithmetic around the network (reference run_inference.py:121-183, utils.py:45-76).  Equality with the
  * host libraries is the contract: every step is integer or fixed fp32 / fp64 arithmetic.
  * dn_imresize_u8 = scipy.misc.imresize(frame, (h, w)) for a ragged batch of RGB uint8 frames: frame b is H_b x W_b x 3 bytes at byte offset

@@ -13,7 +13,7 @@ LIB_PATH = pathlib.Path(os.environ.get("DISPNET_HIP_LIB", _PKG / "libdispnet_hip
 # ABI version this binding was written against (include/dispnet_hip.h: dn_version(), bumped on any signature / struct change).
 # load() refuses a library that reports anything else: a stale .so (DISPNET_HIP_LIB, a build that did not re-run) would otherwise
 # read struct fields past the end of what this binding fills in and mis-marshal arguments -- silent memory corruption, not an error.
-EXPECTED_ABI = 25
+EXPECTED_ABI = 26
 
 DN_MAX_OPERANDS = 3
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_ELU, ACT_SIGMOID_AFFINE = 0, 1, 2, 3, 4
@@ -225,6 +225,9 @@ SIGNATURES = {
     "dn_zoom3_prefilter": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "dn_zoom3_clip": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _f, _f, _vp, _vp]),
     "dn_eval_errors": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f, _vp, _vp]),
+    "dn_mono2_post_process": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "dn_bilinear_recip_ragged": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "dn_eval_errors_clamp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f, _f, _f, _vp, _vp]),
     "dn_snippet_gather": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "dn_pose_eval_sfm": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "dn_pose_eval_mono2": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),

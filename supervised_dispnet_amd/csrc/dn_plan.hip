@@ -387,7 +387,7 @@ static const ConvFamily* plan_route(const dn_conv_desc* d, IgemmParams* p) {
 
 extern "C" {
 
-int dn_version(void) { return 25; }
+int dn_version(void) { return 26; }
 
 void dn_reload_knobs(void) {
   std::lock_guard<std::mutex> lock(dn::g_knobs_mu);

@@ -8,6 +8,11 @@ dn_zoom3_prefilter -> dn_zoom3_clip -> dn_eval_errors.  Ground truths of a batch
 375x1242, 376x1241), so the zoomed predictions, the ground truth and the masks share one ragged layout: image b is H_b x W_b elements
 at element offset off[b], offsets aligned to RAGGED_ALIGN elements.  [B][8] floats come back; the network-resolution depth only when
 the caller keeps predictions.
+
+With protocol "monodepth2" (eval_disp.py --protocol monodepth2 [--post-process]) the chain after the forward is
+monodepth2's evaluate_depth.py instead: [one forward at 2B and dn_mono2_post_process ->] dn_bilinear_recip_ragged (the disparity resized
+bilinearly to each ground-truth size, then inverted) -> dn_eval_errors_clamp (scale first, clamp last).  The mono2_* functions below state
+the same arithmetic in numpy, per image: the yardstick of the device chain and the chain that runs without --eval-batch.
 """
 import ctypes
 
@@ -70,6 +75,108 @@ def scale_mode(args):
     return SCALE_NONE, 1.0
 
 
+PROTOCOLS = ("reference", "monodepth2")
+SID_NETWORKS = ("DORN", "disp_vgg_BN_DORN")
+
+
+def check_protocol(protocol, post_process, gt_type="KITTI", network=None):
+    """What --protocol monodepth2 covers; a ValueError names the flag that does not fit."""
+    if protocol not in PROTOCOLS:
+        raise ValueError("--protocol must be one of {}".format(", ".join(PROTOCOLS)))
+    if post_process and protocol != "monodepth2":
+        raise ValueError("--post-process belongs to monodepth2's evaluation; add --protocol monodepth2")
+    if protocol == "monodepth2" and gt_type == "NYU":
+        raise ValueError("--protocol monodepth2 is KITTI's evaluation; it does not take --gt-type NYU")
+    if protocol == "monodepth2" and network in SID_NETWORKS:
+        raise ValueError("--protocol monodepth2 resizes a disparity; --network {} decodes ordinal labels into depth".format(network))
+
+
+# ---- monodepth2's evaluate_depth.py per image on the host (DESIGN.md section 22): the arithmetic of dn_mono2_post_process,
+# dn_bilinear_recip_ragged and dn_eval_errors_clamp in numpy -- fp64 from the fp32 inputs, rounded where the kernels round.  The
+# yardstick of the device chain, and what eval_disp.py --protocol monodepth2 runs without --eval-batch.
+def mono2_ramps(w):
+    """-> (lm, rm) float64 [w]: lm = 1 - clip(20 (x / (w - 1) - 0.05), 0, 1), rm its mirror; w >= 2."""
+    if w < 2:
+        raise ValueError("post-processing needs at least two columns")
+    lm = 1.0 - np.clip(20.0 * (np.arange(w, dtype=np.float64) / (w - 1) - 0.05), 0.0, 1.0)
+    return lm, lm[::-1].copy()
+
+
+def mono2_post_process(disp, disp_mirrored):
+    """disp and the network's output for the mirrored frame (as it came: still mirrored), float32 [h, w] -> float32 [h, w]."""
+    L = np.asarray(disp, dtype=np.float32).astype(np.float64)
+    R = np.asarray(disp_mirrored, dtype=np.float32).astype(np.float64)[:, ::-1]
+    lm, rm = mono2_ramps(L.shape[1])
+    return (rm * L + lm * R + (1.0 - lm - rm) * (0.5 * (L + R))).astype(np.float32)
+
+
+def bilinear_taps(n, O):
+    """One axis of the half-pixel bilinear resize n -> O: (i0, i1 int64 [O], f float64 [O]), edges replicated."""
+    s = (np.arange(O, dtype=np.float64) + 0.5) * (float(n) / float(O)) - 0.5
+    fl = np.floor(s)
+    f, i0 = s - fl, fl.astype(np.int64)
+    f[i0 < 0] = 0.0
+    i0[i0 < 0] = 0
+    f[i0 >= n - 1] = 0.0
+    i0[i0 >= n - 1] = n - 1
+    return i0, np.minimum(i0 + 1, n - 1), f
+
+
+def mono2_resize_recip(disp, shape):
+    """float32 [h, w] -> the depth 1 / resize(disp) as float32 [H, W]: rows blended in x, then the two results in y, one division."""
+    d = np.asarray(disp, dtype=np.float32).astype(np.float64)
+    y0, y1, fy = bilinear_taps(d.shape[0], int(shape[0]))
+    x0, x1, fx = bilinear_taps(d.shape[1], int(shape[1]))
+    top = (1.0 - fx) * d[y0][:, x0] + fx * d[y0][:, x1]
+    bot = (1.0 - fx) * d[y1][:, x0] + fx * d[y1][:, x1]
+    return (1.0 / ((1.0 - fy)[:, None] * top + fy[:, None] * bot)).astype(np.float32)
+
+
+def mono2_errors(gt, depth, mask, mode, fixed, lo, hi):
+    """Steps 4-6 -> (float64 [7], float32 scale): the scale from the unclamped depth, fp32(depth * scale) clamped to [lo, hi], thresholds
+    in fp32, the four means in fp64 (dn_eval_errors' rule)."""
+    mask = np.asarray(mask, dtype=bool)
+    g, p = np.asarray(gt)[mask].astype(np.float32), np.asarray(depth, dtype=np.float32)[mask]
+    scale = {SCALE_NONE: np.float32(1), SCALE_FIXED: np.float32(fixed)}.get(mode)
+    if g.size == 0:
+        return np.full(7, np.nan), np.float32(np.nan) if scale is None else scale
+    if scale is None:
+        scale = median_scale_f32(g, p)
+    ps = np.minimum(np.maximum(p * scale, np.float32(lo)), np.float32(hi))
+    thr = np.maximum(g / ps, ps / g)
+    gd, pd = g.astype(np.float64), ps.astype(np.float64)
+    d, dl = gd - pd, np.log(gd) - np.log(pd)
+    return np.array([np.mean(np.abs(d) / gd), np.mean(d * d / gd), np.sqrt(np.mean(d * d)), np.sqrt(np.mean(dl * dl)),
+                     np.mean(thr < np.float32(1.25)), np.mean(thr < np.float32(1.5625)), np.mean(thr < np.float32(1.953125))]), scale
+
+
+def mono2_host_chain(disp, disp_mirrored, gt, mask, mode, fixed, lo, hi):
+    """One image, steps 1-6 -> (float64 [7], scale, the disparity the resize took); disp_mirrored None: no post-processing."""
+    if disp_mirrored is not None:
+        disp = mono2_post_process(disp, disp_mirrored)
+    errs, scale = mono2_errors(gt, mono2_resize_recip(disp, np.shape(gt)), mask, mode, fixed, lo, hi)
+    return errs, scale, np.asarray(disp, dtype=np.float32)
+
+
+@torch.no_grad()
+def mono2_evaluate_sample(args, disp_net, sample, device, min_depth, max_depth, post_process=False):
+    """test_disp.evaluate_sample's place under --protocol monodepth2: the frame prepared and normalised as there, one forward at batch 1
+    (2 with post-processing: the frame and its mirror image), the disparity copied back, the host chain above.
+    -> (float64 [7], scale, depth 1 / disp at network resolution)."""
+    from .data import normalization
+    frame = prepare_frame(args, sample)
+    t = torch.from_numpy(np.ascontiguousarray(np.transpose(frame, (2, 0, 1)))).float()
+    mean, std = normalization(args.imagenet_normalization, args.monodepth2)
+    t = ((t / 255 - torch.tensor(mean).view(3, 1, 1)) / torch.tensor(std).view(3, 1, 1)).unsqueeze(0)
+    if post_process:
+        t = torch.cat([t, torch.flip(t, dims=[3])])
+    disp = disp_net(t.to(device)).float().cpu().numpy()[:, 0]
+    gt, mask = sample_ground_truth(args, sample, min_depth, max_depth)
+    mode, fixed = scale_mode(args)
+    errs, scale, used = mono2_host_chain(disp[0], disp[1] if post_process else None, gt, mask, mode, fixed, min_depth, max_depth)
+    return errs, scale, np.float32(1) / used
+
+
 def network_size(args):
     return (256, 352) if args.gt_type == "NYU" else (args.img_height, args.img_width)   # NYU size hard-coded (test_disp.py:154-155)
 
@@ -124,13 +231,17 @@ class DeviceEvaluator(object):
     """evaluate(samples) -> (errors float32 [7, n], [depth at network resolution] or None per sample).  Workspaces grow to the largest
     batch seen and are reused."""
 
-    def __init__(self, args, disp_net, device, min_depth, max_depth, keep_depth=None):
+    def __init__(self, args, disp_net, device, min_depth, max_depth, keep_depth=None, protocol=None, post_process=None):
         from .data import normalization
         self.args, self.net, self.device = args, disp_net, torch.device(device)
         self.lo, self.hi = float(min_depth), float(max_depth)
         self.keep_depth = (args.output_dir is not None) if keep_depth is None else keep_depth
         self.mode, self.fixed = scale_mode(args)
-        self.sid = args.network in ("DORN", "disp_vgg_BN_DORN")
+        self.sid = args.network in SID_NETWORKS
+        # "monodepth2": evaluate_depth.py's chain (DESIGN.md section 22) in place of test_disp.py's; post_process: its "+pp" rows
+        self.protocol = getattr(args, "protocol", "reference") if protocol is None else protocol
+        self.post_process = bool(getattr(args, "post_process", False) if post_process is None else post_process)
+        check_protocol(self.protocol, self.post_process, args.gt_type, args.network)
         mean, std = normalization(args.imagenet_normalization, args.monodepth2)
         self.mean_h, self.std_h = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
         self.mean_d = torch.tensor(mean, dtype=torch.float32, device=self.device)
@@ -197,6 +308,46 @@ class DeviceEvaluator(object):
                   self.lo, self.hi, zoomed.data_ptr(), st)
         return zoomed, d_off
 
+    def mirrored(self, img):
+        """[N, 3, h, w] -> [2N, 3, h, w]: planes N .. 2N-1 are the same frames mirrored along the width (dn_flip_w over 3N planes with
+        every flag set), so that the post-processing costs ONE forward at 2N."""
+        N, C, h, w = img.shape
+        img = img.contiguous()
+        both = self._buf("img2", 2 * N * C * h * w, torch.float32).view(2 * N, C, h, w)
+        both[:N].copy_(img)
+        flags = self._buf("flip", N * C, torch.uint8)
+        flags.fill_(1)
+        _lib.call("dn_flip_w", img.data_ptr(), flags.data_ptr(), N * C, h, w, both[N:].data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        return both
+
+    @torch.no_grad()
+    def forward_disp(self, img):
+        """One eval-mode forward -> the disparity [n, h, w] fp32, contiguous."""
+        disp = self.net(img)
+        return disp.reshape(img.shape[0], disp.shape[-2], disp.shape[-1]).contiguous().float()
+
+    @torch.no_grad()
+    def predict_disp(self, img):
+        """The disparity monodepth2's chain resizes, [B, h, w] fp32: the forward at B, or with post-processing the forward at 2B (the
+        frames and their mirror images) blended by dn_mono2_post_process."""
+        if not self.post_process:
+            return self.forward_disp(img)
+        B = img.shape[0]
+        both = self.forward_disp(self.mirrored(img))
+        _, h, w = both.shape
+        out = self._buf("pp", B * h * w, torch.float32).view(B, h, w)
+        _lib.call("dn_mono2_post_process", both.data_ptr(), B, h, w, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        return out
+
+    def resize_recip(self, disp, hw, off, total):
+        """disp [B, h, w] on the device -> the ragged depths 1 / resize(disp) at the ground-truth sizes (a view of a reused workspace)."""
+        B, h, w = disp.shape
+        d_hw, d_off = self._upload("hw", hw), self._upload("off", off)
+        resized = self._buf("zoomed", total, torch.float32)
+        _lib.call("dn_bilinear_recip_ragged", disp.data_ptr(), B, h, w, d_hw.data_ptr(), d_off.data_ptr(), int(hw[:, 0].max()),
+                  int(hw[:, 1].max()), resized.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        return resized, d_off
+
     @torch.no_grad()
     def evaluate(self, samples):
         B = len(samples)
@@ -209,11 +360,21 @@ class DeviceEvaluator(object):
         d_gt = self._upload("gt", pack_ragged(gts, np.float32, off, total))
         d_mask = self._upload("mask", pack_ragged(masks, np.uint8, off, total))
         d_npix = self._upload("npix", npix)
-        depth = self.predict_depth(img)
-        zoomed, d_off = self.zoom_clip(depth, hw, off, total)
         out = self._buf("out", B * 8, torch.float32)
-        _lib.call("dn_eval_errors", d_gt.data_ptr(), zoomed.data_ptr(), d_mask.data_ptr(), d_off.data_ptr(), d_npix.data_ptr(), B, self.mode,
-                  self.fixed, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        if self.protocol == "monodepth2":
+            disp = self.predict_disp(img)
+            resized, d_off = self.resize_recip(disp, hw, off, total)
+            _lib.call("dn_eval_errors_clamp", d_gt.data_ptr(), resized.data_ptr(), d_mask.data_ptr(), d_off.data_ptr(), d_npix.data_ptr(), B,
+                      self.mode, self.fixed, self.lo, self.hi, out.data_ptr(), st)
+            if self.keep_depth:
+                from . import functional
+                depth = functional.reciprocal(disp)
+        else:
+            depth = self.predict_depth(img)
+            zoomed, d_off = self.zoom_clip(depth, hw, off, total)
+            _lib.call("dn_eval_errors", d_gt.data_ptr(), zoomed.data_ptr(), d_mask.data_ptr(), d_off.data_ptr(), d_npix.data_ptr(), B, self.mode,
+                      self.fixed, out.data_ptr(), st)
         res = out.view(B, 8).cpu().numpy()
         self.scales = res[:, 7].copy()
         pred = list(depth.cpu().numpy()) if self.keep_depth else [None] * B
